@@ -68,3 +68,66 @@ def test_bench_line_fields_of_round_5(monkeypatch):
     src = open(os.path.join(ROOT, "bench.py")).read()
     for field in ('"traffic"', '"launches_per_step"', '"kernel_ms_note"', '"traffic_note"', '"cores"', '"ms_per_step_cold"', '"other_configs"'):
         assert field in src, field
+
+
+def test_plain_run_is_lean_and_full_is_opt_in(monkeypatch):
+    """a plain run times the steps and prints the headline; everything else is behind --full; --steps really is the number of timed steps"""
+    import pytest
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse_args()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse_args()
+    assert a.full is True and a.dump_outputs == "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse_args()
+
+
+def test_dump_outputs_do_not_depend_on_where_the_blocks_lie(tmp_path):
+    """--dump-outputs: the index, a seeded sample of C's blocks with their values and the counts, the same whatever order the library put
+    the blocks in its data area (C built by the CPU oracle, held as CPU tensors; the engine's checksum stubbed)"""
+    import numpy as np
+    import torch
+    import bench
+    from dbcsr_amd.matrix import DbcsrMatrix
+    from oracle import oracle as O
+    A, B, Cm = O.perf_case(700, 700, 700, 0.8, 0.8, 0.8, [1, 13, 1, 23, 1, 32], [1, 13, 1, 23, 1, 32], [1, 13, 1, 23, 1, 32])
+    ref, info = O.multiply("N", "N", 1.0, A, B, 1.0, Cm)
+    rs, cs = ref.row_sizes, ref.col_sizes
+    rows = np.repeat(np.arange(len(rs)), np.diff(ref.row_p))
+    n = rs[rows].astype(np.int64) * cs[ref.col_i].astype(np.int64)
+    # the same matrix with its blocks stored in reverse order
+    rev_p = np.zeros(len(n), np.int64)
+    rev_p[::-1] = np.concatenate([[0], np.cumsum(n[::-1])[:-1]])
+    rev = np.empty_like(ref.data)
+    for k in range(len(n)):
+        rev[rev_p[k]:rev_p[k] + n[k]] = ref.data[ref.blk_p[k]:ref.blk_p[k] + n[k]]
+
+    class Eng:
+        def checksum(self, M):
+            return float((M.data ** 2).sum()), 0.0
+
+    class Counts:
+        flop, nproducts, c_nblks, c_nze = info["flop"], info["nproducts"], len(n), int(n.sum())
+
+    t = torch.as_tensor
+    for name, bp, data in (("a", ref.blk_p, ref.data), ("b", rev_p, rev)):
+        C = DbcsrMatrix(t(rs), t(cs), t(ref.row_p), t(ref.col_i), t(np.asarray(bp, np.int64)), t(data))
+        bench.dump_outputs(str(tmp_path / name), Eng(), C, Counts())
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b")) and "c_sample_values.npy" in files and "counts.npy" in files
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and (np.array_equal(x, y) or f == "c_checksum.npy" and np.allclose(x, y, rtol=1e-12)), f
+    blocks = np.load(tmp_path / "a" / "c_sample_blocks.npy").astype(np.int64)
+    vals = np.load(tmp_path / "a" / "c_sample_values.npy")
+    assert len(blocks) == min(len(n), bench.DUMP_SAMPLE_BLOCKS)
+    pos = 0
+    for r, c in blocks:
+        k = ref.row_p[r] + int(np.searchsorted(ref.col_i[ref.row_p[r]:ref.row_p[r + 1]], c))
+        m = int(rs[r]) * int(cs[c])
+        assert ref.col_i[k] == c and np.array_equal(vals[pos:pos + m], ref.data[ref.blk_p[k]:ref.blk_p[k] + m])
+        pos += m
+    assert pos == len(vals)

@@ -3,7 +3,7 @@
 # peer" to a bench line, stage by stage, stopping at the first stage that fails:
 #   1. tools/comm_selfcheck.py   all-pairs grouped exchange + sizes allgather through the C-ABI transport, checked against host copies, GB/s per link
 #   2. tools/run_dist_check.py   every schedule (gather, ticks, colpipe, distributed input) with transport=native, against the CPU oracle's product
-#   3. bench.py --gpus N         the benchmark line (carries rccl_ranks, GB/s per link of the exchange alone, the overlap fraction)
+#   3. bench.py --gpus N --full  the benchmark line (carries rccl_ranks, GB/s per link of the exchange alone, the overlap fraction)
 #   tools/scale_first_contact.sh [N] [--dry-run]      N defaults to the number of visible devices; --dry-run prints the commands only
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 N=""; DRY=0
@@ -27,7 +27,7 @@ run 1_comm_selfcheck $TR --master-port $(port) tools/comm_selfcheck.py nccl nati
 for mode in gather ticks colpipe gather+dist; do
   run 2_dist_check_${mode/+/_} $TR --master-port $(port) tools/run_dist_check.py nccl $mode native
 done
-run 3_bench python bench.py --gpus $N --steps 10 --warmup 2 --dist-transport native
+run 3_bench python bench.py --gpus $N --steps 10 --warmup 2 --dist-transport native --full
 [ $DRY = 1 ] || grep '^{"metric"' $O/3_bench.out | python -c "
 import json, sys
 d = json.loads(sys.stdin.readline()); c = d.get('comm') or {}
