@@ -6,13 +6,7 @@
 // ----------------------------------------------------------------------------
 // host side
 // ----------------------------------------------------------------------------
-// Exact-size kernels are instantiated for every cube from 9 to 32 (the reference compiles one kernel per (m, n, k) at run
-// time; here the list is fixed at build time and every other case -- mixed sizes, blocks above 32 -- runs the generic kernels; measured on 4 x 4 blocks the generic kernel is 7 % faster, so sizes
-// up to 8 are left to it).
-#define DBCSR_AMD_HOT_SIZES(X) \
-  X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) X(19) X(20) X(21) X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(29) X(30) X(31) X(32)
-
-#define DBCSR_AMD_DMA_SIZES(X) X(13) X(16) X(23) X(32)
+// (the instance lists -- DBCSR_AMD_HOT_SIZES and their like -- and the predicates that answer for them are in mm_choose.h)
 
 // one wave per C block, only the blocks that are NOT m x n: their squared Frobenius norm (the exact-size kernel wrote the others')
 __global__ void __launch_bounds__(256) block_norms_other_sizes(const Desc* __restrict__ descs, int64_t nblk, const double* __restrict__ c_data,
@@ -55,36 +49,30 @@ __global__ void __launch_bounds__(256) block_norms_unserved_classes(const Desc* 
   if (lane == 0) norms[cb] = ss;
 }
 
-static bool launch_hot_f64(int m, int n, int k, dim3 grid, size_t lds_bytes, hipStream_t st, const Desc* descs, int64_t nblk,
-                           const Entry* entries, const double* a_data, const double* b_data, double* c_out, const double* c_in,
-                           double alpha, double beta, int lds_a, int lds_wave, int dbg, const int* order, const Work* work, int wg_waves,
-                           double* norms, int variant) {
-  if (m != n || m != k) return false;
+// Every launcher takes the call's operands (NumericArgs, mm_mid.h) and its geometry, mostly as the NumericChoice made (mm_choose.h); each returns false
+// when it has no instance for the sizes -- the choice asked the predicate beside the instance list first, so for the caller that is an error.
+
+// exact-size kernel: flags / variant are the caller's (the launches that leave the dominant size alone pass their own)
+static bool launch_hot_f64(const NumericArgs<double>& p, const NumericChoice& c, int m, int n, int k, int flags, int variant) {
+  if (!hot_f64_has(m, n, k)) return false;
+  const dim3 grid(c.grid), block(64 * c.ww);
 #ifdef DBCSR_AMD_EXPERIMENTS
   // profiling variants exist for the benchmark's block size only (ablation switches; unpaired fragment reads)
   if (m == 23 && variant >= 1 && variant <= 6) {
-#define DBCSR_HOT_VARIANT(V_)                                                                                                              \
-  hipLaunchKernelGGL((mm_numeric_f64_hot<23, 23, 23, V_>), grid, dim3(64 * wg_waves), lds_bytes, st, descs, nblk, entries, a_data, b_data, c_out, \
-                     c_in, alpha, beta, lds_a, lds_wave, dbg, order, work, norms)
-    switch (variant) {
-      case 1: DBCSR_HOT_VARIANT(1); break;
-      case 2: DBCSR_HOT_VARIANT(2); break;
-      case 3: DBCSR_HOT_VARIANT(3); break;
-      case 4: DBCSR_HOT_VARIANT(4); break;
-      case 5: DBCSR_HOT_VARIANT(5); break;
-      default: DBCSR_HOT_VARIANT(6); break;
-    }
-#undef DBCSR_HOT_VARIANT
+    auto kern = variant == 1 ? mm_numeric_f64_hot<23, 23, 23, 1> : variant == 2 ? mm_numeric_f64_hot<23, 23, 23, 2> : variant == 3 ? mm_numeric_f64_hot<23, 23, 23, 3> :
+                variant == 4 ? mm_numeric_f64_hot<23, 23, 23, 4> : variant == 5 ? mm_numeric_f64_hot<23, 23, 23, 5> : mm_numeric_f64_hot<23, 23, 23, 6>;
+    hipLaunchKernelGGL(kern, grid, block, c.lds_bytes, p.st, p.descs, p.nblk, p.entries, p.a, p.b, p.c_out, p.c_in, p.alpha, p.beta, c.lds_a, c.lds_wave, flags,
+                       p.order, p.work, p.norms);
     return true;
   }
 #else
   (void)variant;
 #endif
   switch (m) {
-#define DBCSR_HOT_CASE(S_)                                                                                                      \
-  case S_:                                                                                                                      \
-    hipLaunchKernelGGL((mm_numeric_f64_hot<S_, S_, S_, 0>), grid, dim3(64 * wg_waves), lds_bytes, st, descs, nblk, entries, a_data, b_data, c_out, \
-                       c_in, alpha, beta, lds_a, lds_wave, dbg, order, work, norms);                                            \
+#define DBCSR_HOT_CASE(S_)                                                                                                                          \
+  case S_:                                                                                                                                          \
+    hipLaunchKernelGGL((mm_numeric_f64_hot<S_, S_, S_, 0>), grid, block, c.lds_bytes, p.st, p.descs, p.nblk, p.entries, p.a, p.b, p.c_out, p.c_in,  \
+                       p.alpha, p.beta, c.lds_a, c.lds_wave, flags, p.order, p.work, p.norms);                                                     \
     return true;
     DBCSR_AMD_HOT_SIZES(DBCSR_HOT_CASE)
 #undef DBCSR_HOT_CASE
@@ -94,43 +82,30 @@ static bool launch_hot_f64(int m, int n, int k, dim3 grid, size_t lds_bytes, hip
 
 #ifdef DBCSR_AMD_EXPERIMENTS
 // LDS-DMA variant of the exact-size kernel (mm_dma.h): S ring slots per wave, one wave per workgroup
-template <int S_>
-static bool launch_dma_f64_s(int m, int n, int k, unsigned npos, hipStream_t st, const Desc* descs, int64_t nblk, const Entry* entries,
-                             const double* a_data, const double* b_data, double* c_out, const double* c_in, double alpha, double beta,
-                             int skip_empty, const int* order) {
-  if (m != n || m != k) return false;
-  switch (m) {
-#define DBCSR_DMA_CASE(S__)                                                                                                   \
-  case S__:                                                                                                                   \
-    hipLaunchKernelGGL((mm_numeric_f64_dma<S__, S__, S__, S_>), dim3(npos), dim3(64), (DmaRing<S__, S__, S__, S_>::BYTES), st, descs, \
-                       nblk, entries, a_data, b_data, c_out, c_in, alpha, beta, skip_empty, order);                           \
+static bool launch_dma_f64(const NumericArgs<double>& p, const NumericChoice& c, int S, int m, int n, int k) {
+  if (!dma_f64_has(S, m, n, k)) return false;
+  switch (S * 64 + m) {
+#define DBCSR_DMA_CASE(R_, S_)                                                                                                               \
+  case R_ * 64 + S_:                                                                                                                          \
+    hipLaunchKernelGGL((mm_numeric_f64_dma<S_, S_, S_, R_>), dim3(c.grid), dim3(64), (DmaRing<S_, S_, S_, R_>::BYTES), p.st, p.descs, p.nblk, \
+                       p.entries, p.a, p.b, p.c_out, p.c_in, p.alpha, p.beta, c.flags, p.order);                                              \
     return true;
-    DBCSR_AMD_DMA_SIZES(DBCSR_DMA_CASE)
+#define DBCSR_DMA_RINGS(S_) DBCSR_DMA_CASE(2, S_) DBCSR_DMA_CASE(3, S_) DBCSR_DMA_CASE(4, S_)
+    DBCSR_AMD_DMA_SIZES(DBCSR_DMA_RINGS)
+#undef DBCSR_DMA_RINGS
 #undef DBCSR_DMA_CASE
-    default: return false;
-  }
-}
-static bool launch_dma_f64(int S, int m, int n, int k, unsigned npos, hipStream_t st, const Desc* descs, int64_t nblk,
-                           const Entry* entries, const double* a_data, const double* b_data, double* c_out, const double* c_in,
-                           double alpha, double beta, int skip_empty, const int* order) {
-  switch (S) {
-    case 2: return launch_dma_f64_s<2>(m, n, k, npos, st, descs, nblk, entries, a_data, b_data, c_out, c_in, alpha, beta, skip_empty, order);
-    case 3: return launch_dma_f64_s<3>(m, n, k, npos, st, descs, nblk, entries, a_data, b_data, c_out, c_in, alpha, beta, skip_empty, order);
-    case 4: return launch_dma_f64_s<4>(m, n, k, npos, st, descs, nblk, entries, a_data, b_data, c_out, c_in, alpha, beta, skip_empty, order);
     default: return false;
   }
 }
 #endif
 
-static bool launch_hot_f32(int m, int n, int k, dim3 grid, int wg_waves, hipStream_t st, const Desc* descs, int64_t nblk, const Entry* entries,
-                           const float* a_data, const float* b_data, float* c_out, const float* c_in, float alpha, float beta,
-                           int skip_empty, const int* order) {
-  if (m != n || m != k) return false;
+static bool launch_hot_f32(const NumericArgs<float>& p, const NumericChoice& c, int m, int n, int k) {
+  if (!hot_f64_has(m, n, k)) return false;   // (the same cubes as fp64)
   switch (m) {
-#define DBCSR_HOT_CASE(S_)                                                                                                     \
-  case S_:                                                                                                                     \
-    hipLaunchKernelGGL((mm_numeric_f32_hot<S_, S_, S_>), grid, dim3(64 * wg_waves), f32_lds_bytes(wg_waves), st, descs, nblk, entries, a_data, b_data, c_out, c_in, \
-                       alpha, beta, skip_empty, order);                                                                        \
+#define DBCSR_HOT_CASE(S_)                                                                                                                          \
+  case S_:                                                                                                                                          \
+    hipLaunchKernelGGL((mm_numeric_f32_hot<S_, S_, S_>), dim3(c.grid), dim3(64 * c.ww), f32_lds_bytes(c.ww), p.st, p.descs, p.nblk, p.entries, p.a, \
+                       p.b, p.c_out, p.c_in, p.alpha, p.beta, c.flags, p.order);                                                                    \
     return true;
     DBCSR_AMD_HOT_SIZES(DBCSR_HOT_CASE)
 #undef DBCSR_HOT_CASE
@@ -139,43 +114,35 @@ static bool launch_hot_f32(int m, int n, int k, dim3 grid, int wg_waves, hipStre
 }
 
 // the direct form of the fp32 exact-size kernel (mm_numeric_f32.h, round 5): cubes whose k is a multiple of 8
-static bool launch_hot_f32_direct(int m, int n, int k, dim3 grid, int wg_waves, hipStream_t st, const Desc* descs, int64_t nblk, const Entry* entries,
-                                  const float* a_data, const float* b_data, float* c_out, const float* c_in, float alpha, float beta,
-                                  int skip_empty, const int* order, bool slim = false) {
-  if (m != n || m != k) return false;
-  if (slim) {   // every C block has the dominant size: LDS for the B images only
-    switch (m) {
-#define DBCSR_SLIM_CASE(S_)                                                                                                    \
-  case S_:                                                                                                                     \
-    hipLaunchKernelGGL((mm_numeric_f32_direct_slim<S_, S_, S_>), grid, dim3(64 * wg_waves), (size_t)wg_waves * f32d_wave_floats(S_) * sizeof(float), st, \
-                       descs, nblk, entries, a_data, b_data, c_out, c_in, alpha, beta, skip_empty, order);                     \
+static bool launch_hot_f32_direct(const NumericArgs<float>& p, const NumericChoice& c, int m, int n, int k, int flags, bool slim) {
+  if (!f32_direct_has(m, n, k)) return false;
+  switch (m) {   // slim: every C block has the dominant size, LDS for the B images only
+#define DBCSR_DIRECT_CASE(S_)                                                                                                                      \
+  case S_:                                                                                                                                         \
+    hipLaunchKernelGGL((slim ? mm_numeric_f32_direct_slim<S_, S_, S_> : mm_numeric_f32_direct<S_, S_, S_>), dim3(c.grid), dim3(64 * c.ww),         \
+                       slim ? (size_t)c.ww * f32d_wave_floats(S_) * sizeof(float) : f32_lds_bytes(c.ww), p.st, p.descs, p.nblk, p.entries, p.a, p.b, \
+                       p.c_out, p.c_in, p.alpha, p.beta, flags, p.order);                                                                          \
     return true;
-      DBCSR_SLIM_CASE(16) DBCSR_SLIM_CASE(24) DBCSR_SLIM_CASE(32)
-#undef DBCSR_SLIM_CASE
-      default: return false;
-    }
-  }
-  switch (m) {
-#define DBCSR_DIRECT_CASE(S_)                                                                                                  \
-  case S_:                                                                                                                     \
-    hipLaunchKernelGGL((mm_numeric_f32_direct<S_, S_, S_>), grid, dim3(64 * wg_waves), f32_lds_bytes(wg_waves), st, descs, nblk, entries, a_data, b_data, \
-                       c_out, c_in, alpha, beta, skip_empty, order);                                                           \
-    return true;
-    DBCSR_DIRECT_CASE(16) DBCSR_DIRECT_CASE(24) DBCSR_DIRECT_CASE(32)
+    DBCSR_AMD_F32_DIRECT_SIZES(DBCSR_DIRECT_CASE)
 #undef DBCSR_DIRECT_CASE
     default: return false;
   }
 }
 
+// fp32, any sizes up to 32, on the positions of `p.order` that `grid` workgroups of c.ww waves cover
+static void launch_lds_f32(const NumericArgs<float>& p, const NumericChoice& c, unsigned grid) {
+  hipLaunchKernelGGL(mm_numeric_f32_lds, dim3(grid), dim3(64 * c.ww), f32_lds_bytes(c.ww), p.st, p.descs, p.nblk, p.entries, p.a, p.b, p.c_out, p.c_in,
+                     p.alpha, p.beta, c.flags, p.order);
+}
+
 // blocks of 33 ... 80: sub-blocks of TM x TN tiles per wave, 2 x 2 waves per C block (mm_numeric_f64_big.h)
-static bool launch_big_f64(int tm, int tn, unsigned npos, hipStream_t st, const Desc* descs, int64_t nblk, const Entry* entries, const double* a_data,
-                           const double* b_data, double* c_out, const double* c_in, double alpha, double beta, int skip_empty, const int* order) {
-  if (tm < 2 || tm > 5 || tn < 2 || tn > 5 || npos == 0) return false;
+static bool launch_big_f64(const NumericArgs<double>& p, const NumericChoice& c, int tm, int tn) {
+  if (!big_f64_has(tm, tn) || c.grid == 0) return false;
   switch (tm * 8 + tn) {
-#define DBCSR_BIG_CASE(A_, B_)                                                                                                        \
-  case A_ * 8 + B_:                                                                                                                   \
-    hipLaunchKernelGGL((mm_numeric_f64_big<A_, B_>), dim3(npos), dim3(256), (size_t)big_lds_bytes(A_, B_), st, descs, nblk, entries, a_data, b_data, c_out, \
-                       c_in, alpha, beta, skip_empty, order);                                                                         \
+#define DBCSR_BIG_CASE(A_, B_)                                                                                                                  \
+  case A_ * 8 + B_:                                                                                                                             \
+    hipLaunchKernelGGL((mm_numeric_f64_big<A_, B_>), dim3(c.grid), dim3(256), (size_t)big_lds_bytes(A_, B_), p.st, p.descs, p.nblk, p.entries,  \
+                       p.a, p.b, p.c_out, p.c_in, p.alpha, p.beta, c.flags, p.order);                                                           \
     return true;
     DBCSR_BIG_CASE(2, 2) DBCSR_BIG_CASE(2, 3) DBCSR_BIG_CASE(2, 4) DBCSR_BIG_CASE(2, 5)
     DBCSR_BIG_CASE(3, 2) DBCSR_BIG_CASE(3, 3) DBCSR_BIG_CASE(3, 4) DBCSR_BIG_CASE(3, 5)
@@ -184,6 +151,37 @@ static bool launch_big_f64(int tm, int tn, unsigned npos, hipStream_t st, const 
 #undef DBCSR_BIG_CASE
     default: return false;
   }
+}
+
+// any sizes up to 32, one wave per C block, whole blocks staged in the wave's LDS slice; `grid` workgroups of c.ww waves
+static void launch_lds_f64(const NumericArgs<double>& p, const NumericChoice& c, unsigned grid) {
+  auto kern = c.maxt == 1 ? mm_numeric_f64_lds<1> : c.maxt == 2 ? mm_numeric_f64_lds<2> : c.maxt == 3 ? mm_numeric_f64_lds<3> : mm_numeric_f64_lds<4>;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * c.ww), c.lds_bytes, p.st, p.descs, p.nblk, p.entries, p.a, p.b, p.c_out, p.c_in, p.alpha, p.beta, c.lds_a,
+                     c.lds_wave, c.flags, p.order);
+}
+
+// the same with c.group C blocks per wave, the next block's operands in flight (mixed sizes, few products per block)
+static void launch_pipe_f64(const NumericArgs<double>& p, const NumericChoice& c, int64_t npos) {
+  auto kern = c.maxt == 1 ? mm_numeric_f64_pipe<1> : c.maxt == 2 ? mm_numeric_f64_pipe<2> : c.maxt == 3 ? mm_numeric_f64_pipe<3> : mm_numeric_f64_pipe<4>;
+  hipLaunchKernelGGL(kern, dim3(c.grid), dim3(256), c.lds_bytes, p.st, p.descs, p.nblk, p.entries, p.a, p.b, p.c_out, p.c_in, p.alpha, p.beta, c.lds_a,
+                     c.lds_wave, c.flags, p.order, npos, c.group);
+}
+
+// C blocks of at most 4 x 4: four per wave
+static void launch_tiny_f64(const NumericArgs<double>& p, const NumericChoice& c, bool k4) {   // k4: the inner dimension is at most 4 too
+  auto kern = k4 ? mm_numeric_f64_tiny<true> : mm_numeric_f64_tiny<false>;
+  hipLaunchKernelGGL(kern, dim3(c.grid), dim3(256), 0, p.st, p.descs, p.nblk, p.entries, p.a, p.b, p.c_out, p.c_in, p.alpha, p.beta, c.flags, p.order);
+}
+
+// every block dimension at most 8: one 8 x 8 tile per wave, c.depth products in flight, c.group C blocks per wave (mm_numeric_f64_small.h)
+static void launch_small_f64(const NumericArgs<double>& p, const NumericChoice& c, int64_t npos) {
+  const int d = c.depth;
+  auto kern = p.work ? (d == 2 ? mm_numeric_f64_small<2, true> : d == 3 ? mm_numeric_f64_small<3, true> : d == 4 ? mm_numeric_f64_small<4, true> :
+                        d == 6 ? mm_numeric_f64_small<6, true> : mm_numeric_f64_small<8, true>)
+                     : (d == 2 ? mm_numeric_f64_small<2, false> : d == 3 ? mm_numeric_f64_small<3, false> : d == 4 ? mm_numeric_f64_small<4, false> :
+                        d == 6 ? mm_numeric_f64_small<6, false> : mm_numeric_f64_small<8, false>);
+  hipLaunchKernelGGL(kern, dim3(c.grid), dim3(256), 0, p.st, p.descs, p.nblk, p.entries, p.a, p.b, p.c_out, p.c_in, p.alpha, p.beta, c.flags, p.order,
+                     p.work, c.group, npos);
 }
 
 #endif

@@ -14,8 +14,8 @@ int dbcsr_amd_mm_init_c(void* handle, libsmm_acc_data_t datatype, double beta, c
   }
   if (datatype != dbcsr_type_real_8 && datatype != dbcsr_type_real_4) return -10;
   hipStream_t st = stream_of(stream);
-  const int nbr = E->nbr, W = E->W;
-  const int64_t nblk = E->c_nblks;
+  const int nbr = E->facts.nbr, W = E->W;
+  const int64_t nblk = E->facts.c_nblks;
   c_out->nblks = nblk;
   if (nblk == 0) return 0;
   if (E->descs.ensure((size_t)nblk + 1)) return -1;
@@ -291,7 +291,7 @@ int dbcsr_amd_mm_set_canonical_product(void* handle, int on) {
   Engine* E = static_cast<Engine*>(handle);
   if (E) plan_invalidate(E);  // this call uses (or changes what feeds) the engine's work areas: the next multiply runs its own symbolic phase
   if (!E) return -1;
-  E->canonical_c = on ? 1 : 0;
+  E->facts.canonical_c = on ? 1 : 0;
   return 0;
 }
 
@@ -349,14 +349,14 @@ int dbcsr_amd_mm_stats(void* handle, dbcsr_amd_mnk_stat* out, int max_entries, i
   Engine* E = static_cast<Engine*>(handle);
   if (!E || !n_entries || (max_entries > 0 && !out)) return -1;
   *n_entries = 0;
-  if (!E->valid || !E->timed || E->c_nblks == 0) return 0;  // no numeric call yet / nothing to count
+  if (!E->valid || !E->timed || E->facts.c_nblks == 0) return 0;  // no numeric call yet / nothing to count
   hipStream_t st = stream_of(stream);
   if (E->stat_table.ensure(2 * (size_t)kStatSlots + 2)) return -1;
   unsigned long long* keys = E->stat_table.p;
   unsigned long long* counts = keys + kStatSlots;
   int* overflow = reinterpret_cast<int*>(counts + kStatSlots);
   ACC_CHECK(hipMemsetAsync(keys, 0, sizeof(unsigned long long) * (2 * (size_t)kStatSlots + 2), st));
-  hipLaunchKernelGGL(mnk_histogram, grid_for(E->c_nblks), dim3(256), 0, st, E->descs.p, E->c_nblks, E->entries.p, keys, counts, overflow);
+  hipLaunchKernelGGL(mnk_histogram, grid_for(E->facts.c_nblks), dim3(256), 0, st, E->descs.p, E->facts.c_nblks, E->entries.p, keys, counts, overflow);
   std::vector<unsigned long long> host(2 * (size_t)kStatSlots + 2);
   ACC_CHECK(hipMemcpyAsync(host.data(), keys, sizeof(unsigned long long) * host.size(), hipMemcpyDeviceToHost, st));
   ACC_CHECK(hipStreamSynchronize(st));
@@ -419,45 +419,45 @@ int dbcsr_amd_mm_plan_stats(void* handle, int64_t* reused, int64_t* built) {
 int dbcsr_amd_mm_tile_stats(void* handle, int* waves_gave_up, int* list_mismatches) {
   Engine* E = static_cast<Engine*>(handle);
   if (!E) return -1;
-  if (strncmp(E->last_kernel, "mm_numeric_f64_tile", 19) != 0 || !E->tile_flags.p) return 1;
+  if (strncmp(E->last_kernel, "mm_numeric_f64_tile", 19) != 0 || !E->ls.tile_flags.p) return 1;
   int h[4] = {0, 0, 0, 0};
   ACC_CHECK(hipDeviceSynchronize());
-  ACC_CHECK(hipMemcpy(h, E->tile_flags.p, sizeof h, hipMemcpyDeviceToHost));
+  ACC_CHECK(hipMemcpy(h, E->ls.tile_flags.p, sizeof h, hipMemcpyDeviceToHost));
   if (waves_gave_up) *waves_gave_up = h[0];
   if (list_mismatches) *list_mismatches = h[1];
-  if ((E->tile_knobs & 32) && E->tile_times.p) {
+  if ((E->ls.tile_knobs & 32) && E->ls.tile_times.p) {
     unsigned long long t[8];
-    ACC_CHECK(hipMemcpy(t, E->tile_times.p, sizeof t, hipMemcpyDeviceToHost));
+    ACC_CHECK(hipMemcpy(t, E->ls.tile_times.p, sizeof t, hipMemcpyDeviceToHost));
     const double w = t[5] ? (double)t[5] : 1.0;
     fprintf(stderr, "dbcsr_amd tile kernel, mean per wave [ms]: total %.3f = window waits %.3f + operand waits %.3f + multiplies %.3f + epilogues %.3f + rest %.3f (%llu waves)\n",
             t[0] / w * 1e-5, t[1] / w * 1e-5, t[2] / w * 1e-5, t[3] / w * 1e-5, t[4] / w * 1e-5, ((double)t[0] - t[1] - t[2] - t[3] - t[4]) / w * 1e-5, t[5]);
   }
   if (getenv("DBCSR_AMD_MM_TILE_VERBOSE"))
     fprintf(stderr, "dbcsr_amd tile kernel: %d waves gave up, %lld reads of the team counters, %lld products waited for the window (of %lld)\n", h[0],
-            16ll * h[2], 16ll * h[3], (long long)E->nproducts);
+            16ll * h[2], 16ll * h[3], (long long)E->facts.nproducts);
   return 0;
 }
 
 int dbcsr_amd_mm_band_stats(void* handle, int* waits_gave_up, int* list_mismatches) {
   Engine* E = static_cast<Engine*>(handle);
   if (!E) return -1;
-  if (strncmp(E->last_kernel, "mm_numeric_f64_band", 19) != 0 || !E->band_flags.p) return 1;
+  if (strncmp(E->last_kernel, "mm_numeric_f64_band", 19) != 0 || !E->ls.band_flags.p) return 1;
   int h[4] = {0, 0, 0, 0};
   ACC_CHECK(hipDeviceSynchronize());
-  ACC_CHECK(hipMemcpy(h, E->band_flags.p, sizeof h, hipMemcpyDeviceToHost));
+  ACC_CHECK(hipMemcpy(h, E->ls.band_flags.p, sizeof h, hipMemcpyDeviceToHost));
   if (waits_gave_up) *waits_gave_up = h[0];
   if (list_mismatches) *list_mismatches = h[1];
-  if ((E->band_knobs & 1) && E->band_times.p) {
+  if ((E->ls.band_knobs & 1) && E->ls.band_times.p) {
     unsigned long long t[16];
-    ACC_CHECK(hipMemcpy(t, E->band_times.p, sizeof t, hipMemcpyDeviceToHost));
+    ACC_CHECK(hipMemcpy(t, E->ls.band_times.p, sizeof t, hipMemcpyDeviceToHost));
     const double w = t[5] ? (double)t[5] : 1.0;
     fprintf(stderr,
             "dbcsr_amd band kernel, mean per wave [ms]: total %.3f = window waits %.3f + issue and waits for A %.3f + waits for B %.3f + multiplies %.3f + "
             "epilogues %.3f + rest %.3f (%llu waves; %llu of %lld products waited for their B block, %llu fetched it themselves at the last moment; %llu "
             "fetches waited for the window, %llu reads of the team's counters, %d waves switched the throttle off; %lld list entries, shape %d, ring of %d, window %d)\n",
             t[0] / w * 1e-5, t[8] / w * 1e-5, t[1] / w * 1e-5, t[2] / w * 1e-5, t[3] / w * 1e-5, t[4] / w * 1e-5,
-            ((double)t[0] - t[1] - t[2] - t[3] - t[4] - t[8]) / w * 1e-5, t[5], t[7], (long long)E->nproducts, t[6], t[9], t[10], h[3], (long long)E->band_nlist,
-            E->band_shape, E->band_depth, E->band_window);
+            ((double)t[0] - t[1] - t[2] - t[3] - t[4] - t[8]) / w * 1e-5, t[5], t[7], (long long)E->facts.nproducts, t[6], t[9], t[10], h[3], (long long)E->ls.band_nlist,
+            E->ls.band_shape, E->ls.band_depth, E->ls.band_window);
   }
   return 0;
 }

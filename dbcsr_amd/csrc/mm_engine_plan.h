@@ -18,7 +18,7 @@ static void plan_segments(const dbcsr_amd_bcsr* a, const dbcsr_amd_bcsr* b, cons
 static int plan_matches(Engine* E, const dbcsr_amd_bcsr* a, const dbcsr_amd_bcsr* b, const dbcsr_amd_bcsr* c_in, int retain, hipStream_t st) {
   if (!E->use_plan || !E->plan_saved) return 0;
   if (a->nblkrows != E->plan_dims[0] || a->nblkcols != E->plan_dims[1] || b->nblkcols != E->plan_dims[2] || a->nblks != E->plan_nblks[0] ||
-      b->nblks != E->plan_nblks[1] || c_in->nblks != E->plan_nblks[2] || retain != E->plan_retain || E->canonical_c != E->plan_canonical)
+      b->nblks != E->plan_nblks[1] || c_in->nblks != E->plan_nblks[2] || retain != E->plan_retain || E->facts.canonical_c != E->plan_canonical)
     return 0;
   const void* ptr[12];
   long long n[12];
@@ -74,7 +74,7 @@ static int plan_save(Engine* E, const dbcsr_amd_bcsr* a, const dbcsr_amd_bcsr* b
   E->plan_dims[0] = a->nblkrows, E->plan_dims[1] = a->nblkcols, E->plan_dims[2] = b->nblkcols;
   E->plan_nblks[0] = a->nblks, E->plan_nblks[1] = b->nblks, E->plan_nblks[2] = c_in->nblks;
   E->plan_retain = retain;
-  E->plan_canonical = E->canonical_c;
+  E->plan_canonical = E->facts.canonical_c;
   E->plan_counts = counts;
   for (int i = 0; i < 12; ++i) E->plan_ptrs[i] = ptr[i];
   E->plan_stamps[0] = a->index_stamp, E->plan_stamps[1] = b->index_stamp, E->plan_stamps[2] = c_in->index_stamp;

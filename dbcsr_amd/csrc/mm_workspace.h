@@ -17,6 +17,10 @@ template <typename T>
 struct DevBuf {
   T* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;   // (it owns its allocation: released when the engine that holds it is deleted)
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
   int ensure(size_t n) {
     if (n <= cap) return 0;
     if (p) (void)hipFree(p);
