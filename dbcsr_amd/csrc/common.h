@@ -27,6 +27,7 @@ struct KPassMemo {
   int dt = 0, nblkrows = 0, nblkcols = 0, npass = 1;
 };
 KPassMemo* engine_kpass_memo(void* handle);  // mm_engine.hip
+int engine_filter_in_place(void* handle);    // dbcsr_amd_mm_set_filter_in_place (mm_engine.hip)
 
 }  // namespace dbcsr_amd
 

@@ -51,16 +51,23 @@ struct Owned {
   Owned& operator=(const Owned&) = delete;
 };
 
-int alloc_arrays(Owned& o, int nbr, int nbc, const int32_t* rs, const int32_t* cs, int64_t nblks, int64_t nze, size_t esz, bool with_row_p) {
+// col_i and blk_p only: the index of a matrix whose row_p exists already and whose data area comes from elsewhere
+int alloc_index(Owned& o, int nbr, int nbc, const int32_t* rs, const int32_t* cs, int64_t nblks) {
   o.m.nblkrows = nbr;
   o.m.nblkcols = nbc;
   o.m.row_blk_size = rs;
   o.m.col_blk_size = cs;
   o.m.nblks = nblks;
   o.live = true;
-  if (with_row_p && pool_malloc(reinterpret_cast<void**>(&o.m.row_p), sizeof(int32_t) * ((size_t)nbr + 1)) != hipSuccess) return -1;
   if (pool_malloc(reinterpret_cast<void**>(&o.m.col_i), sizeof(int32_t) * (size_t)(nblks > 0 ? nblks : 1)) != hipSuccess) return -1;
   if (pool_malloc(reinterpret_cast<void**>(&o.m.blk_p), sizeof(int64_t) * (size_t)(nblks > 0 ? nblks : 1)) != hipSuccess) return -1;
+  return 0;
+}
+
+int alloc_arrays(Owned& o, int nbr, int nbc, const int32_t* rs, const int32_t* cs, int64_t nblks, int64_t nze, size_t esz, bool with_row_p) {
+  o.live = true;
+  if (with_row_p && pool_malloc(reinterpret_cast<void**>(&o.m.row_p), sizeof(int32_t) * ((size_t)nbr + 1)) != hipSuccess) return -1;
+  if (alloc_index(o, nbr, nbc, rs, cs, nblks)) return -1;
   if (pool_malloc(&o.m.data, esz * (size_t)(nze > 0 ? nze : 1)) != hipSuccess) return -1;
   return 0;
 }
@@ -144,7 +151,8 @@ int symbolic_numeric(void* h, libsmm_acc_data_t dt, double alpha, const dbcsr_am
     return -1;
   // (this helper's product goes straight into the block filter with the same eps: the blocks it will drop need not be written)
   if (eps > 0.0 && !retain) {
-    static const bool off = getenv("DBCSR_AMD_MM_EXPECT_FILTER") && atoi(getenv("DBCSR_AMD_MM_EXPECT_FILTER")) == 0;
+    const char* sw = getenv("DBCSR_AMD_MM_EXPECT_FILTER");  // (read per call, as the Python mirror does: a host may switch it between multiplies)
+    const bool off = sw && atoi(sw) == 0;
     if (!off) dbcsr_amd_mm_expect_filter(h, eps);
   }
   return dbcsr_amd_mm_numeric(h, dt, alpha, a, b, beta, c_in, &out.m, stream);
@@ -358,7 +366,20 @@ int dbcsr_amd_multiply(void* handle, char transa, char transb, libsmm_acc_data_t
     if (alloc_row_p(filtered, prod.m.nblkrows)) return -1;
     int64_t nb = 0, nz = 0;
     if ((rc = dbcsr_amd_bcsr_filter_count(handle, datatype, &prod.m, filter_eps, filtered.m.row_p, &nb, &nz, stream))) return rc;
-    if (nb != prod.m.nblks) {  // (nothing below the threshold: the product is the result, no second copy)
+    if (nb != prod.m.nblks && engine_filter_in_place(handle)) {
+      // dbcsr_amd_mm_set_filter_in_place: only the index is compacted, the kept blocks stay where the product kernel put them
+      if (alloc_index(filtered, prod.m.nblkrows, prod.m.nblkcols, prod.m.row_blk_size, prod.m.col_blk_size, nb)) return -1;
+      filtered.m.data = prod.m.data;  // (borrowed until the kernel below has run; on an early return prod frees it, filtered must not)
+      rc = dbcsr_amd_bcsr_filter_apply_index(handle, &prod.m, &filtered.m, stream);
+      if (rc == 0 && hipStreamSynchronize(st) != hipSuccess) rc = -1;
+      if (rc) {
+        filtered.m.data = nullptr;
+        return rc;
+      }
+      // the data area changes hands: the result owns it together with the new index arrays, the product's own index is freed with prod
+      prod.m.data = nullptr;
+      result = &filtered;
+    } else if (nb != prod.m.nblks) {  // (nothing below the threshold: the product is the result, no second copy)
       if (alloc_arrays(filtered, prod.m.nblkrows, prod.m.nblkcols, prod.m.row_blk_size, prod.m.col_blk_size, nb, nz, esz, false)) return -1;
       if ((rc = dbcsr_amd_bcsr_filter_apply(handle, datatype, &prod.m, &filtered.m, stream))) return rc;
       result = &filtered;

@@ -341,6 +341,20 @@ __global__ void __launch_bounds__(256) filter_compact(const int* __restrict__ ro
   }
 }
 
+// Index-only form of the compaction (dbcsr_amd_bcsr_filter_apply_index): a kept block keeps its place in the data area, only col_i and
+// blk_p are compacted.  One lane per source block (a block row of a large product holds thousands of blocks: a wave per row would
+// leave most of the chip idle); the four reads are coalesced, the two writes monotonic in b.  No element of the data area is touched.
+__global__ void __launch_bounds__(256) filter_compact_index(const int* __restrict__ col_i, const int64_t* __restrict__ blk_p, int64_t nblks,
+                                                            const int* __restrict__ keep, const int64_t* __restrict__ newidx,
+                                                            int64_t new_nblks, int* __restrict__ d_col_i, int64_t* __restrict__ d_blk_p) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= nblks || !keep[b]) return;
+  const int64_t t = newidx[b];
+  if (t < 0 || t >= new_nblks) return;  // (a count that does not belong to these arrays: never write outside dst)
+  d_col_i[t] = col_i[b];
+  d_blk_p[t] = blk_p[b];
+}
+
 // ---- submatrix limits (dbcsr_crop_matrix, src/ops/dbcsr_operations.F:1652-1833; dbcsr_scale with limits) ---------
 struct Window {
   int r0, r1, c0, c1;  // inclusive 0-based element bounds

@@ -60,6 +60,7 @@ int dbcsr_amd_bcsr_crop_count(void* handle, libsmm_acc_data_t datatype, const db
   const int64_t nb = m->nblks;
   E->valid = false;  // shares workspace with the symbolic phase
   E->flt_nblks = nb;
+  E->flt_new_nblks = -1;  // (keep / prod_start now describe the window, not a filter)
   E->crop_win = make_window(m, row_lo, row_hi, col_lo, col_hi);
   E->crop_pending = true;
   if (E->keep.ensure((size_t)nb + 1) || E->blk_nze.ensure((size_t)nb + 1) || E->row_nnz.ensure((size_t)nbr + 1) ||
@@ -137,6 +138,7 @@ int dbcsr_amd_bcsr_filter_count(void* handle, libsmm_acc_data_t datatype, const 
   const int64_t nb = m->nblks;
   E->valid = false;  // shares workspace with the symbolic phase
   E->flt_nblks = nb;
+  E->flt_new_nblks = -1;
   if (E->norms64.ensure((size_t)nb + 1) || E->keep.ensure((size_t)nb + 1) || E->blk_nze.ensure((size_t)nb + 1) ||
       E->row_nnz.ensure((size_t)nbr + 1) || E->prod_start.ensure((size_t)nb + 1) || E->c_blk_p_ws.ensure((size_t)nb + 1) ||
       E->dev_scalars.ensure(16))
@@ -171,6 +173,7 @@ int dbcsr_amd_bcsr_filter_count(void* handle, libsmm_acc_data_t datatype, const 
   ACC_CHECK(hipStreamSynchronize(st));
   *new_nblks = E->host_scalars[0];
   *new_nze = E->host_scalars[1];
+  E->flt_new_nblks = E->host_scalars[0];
   return check(hipGetLastError(), "dbcsr_amd_bcsr_filter_count", __FILE__, __LINE__);
 }
 
@@ -193,6 +196,25 @@ int dbcsr_amd_bcsr_filter_apply(void* handle, libsmm_acc_data_t datatype, const 
   else
     return -10;
   return check(hipGetLastError(), "dbcsr_amd_bcsr_filter_apply", __FILE__, __LINE__);
+}
+
+int dbcsr_amd_bcsr_filter_apply_index(void* handle, const dbcsr_amd_bcsr* src, dbcsr_amd_bcsr* dst, void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (E) plan_invalidate(E);  // this call uses (or changes what feeds) the engine's work areas: the next multiply runs its own symbolic phase
+  if (!E || !src || !dst || E->flt_new_nblks < 0 || E->flt_nblks != src->nblks || dst->data != src->data) return -1;
+  hipStream_t st = stream_of(stream);
+  if (src->nblkrows == 0 || src->nblks == 0 || E->flt_new_nblks == 0) return 0;
+  if (!dst->col_i || !dst->blk_p) return -1;
+  hipLaunchKernelGGL(filter_compact_index, grid_for(src->nblks), dim3(256), 0, st, src->col_i, src->blk_p, (int64_t)src->nblks, E->keep.p,
+                     E->prod_start.p, E->flt_new_nblks, dst->col_i, dst->blk_p);
+  return check(hipGetLastError(), "dbcsr_amd_bcsr_filter_apply_index", __FILE__, __LINE__);
+}
+
+int dbcsr_amd_mm_set_filter_in_place(void* handle, int on) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E) return -1;
+  E->filter_in_place = on ? 1 : 0;
+  return 0;
 }
 
 int dbcsr_amd_bcsr_checksum(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, double* out2, void* stream) {

@@ -112,6 +112,8 @@ struct Engine {
   char last_kernel[96] = "";  // name of the numeric kernel of the last dbcsr_amd_mm_numeric (dbcsr_amd_mm_last_kernel)
   bool timed = false;
   int64_t flt_nblks = 0;
+  int64_t flt_new_nblks = -1;  // blocks the last dbcsr_amd_bcsr_filter_count kept (-1: no count since the handle was made / since a crop count)
+  int filter_in_place = 0;     // dbcsr_amd_mm_set_filter_in_place: dbcsr_amd_multiply's final filter rewrites C's index only
   Window crop_win = {0, 0, 0, 0};       // window of the last dbcsr_amd_bcsr_crop_count
   bool crop_pending = false;
   KPassMemo kpass_memo;  // dbcsr_amd_multiply's k-pass decision for the last stamped A operand (mm_api.hip)
@@ -147,6 +149,7 @@ struct Engine {
 };
 
 KPassMemo* engine_kpass_memo(void* handle) { return handle ? &static_cast<Engine*>(handle)->kpass_memo : nullptr; }
+int engine_filter_in_place(void* handle) { return handle ? static_cast<Engine*>(handle)->filter_in_place : 0; }
 
 // waves per block row for the kernels that stream whole blocks (norms, compaction): enough waves to keep the memory system busy
 static inline int row_split(int64_t nbr, int64_t nblks) {

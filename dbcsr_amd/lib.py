@@ -35,6 +35,7 @@ MM_SYMBOLS = [
     "dbcsr_amd_multiply", "dbcsr_amd_bcsr_release", "dbcsr_amd_bcsr_desymmetrize_count", "dbcsr_amd_bcsr_desymmetrize_apply",
     "dbcsr_amd_bcsr_twin_count", "dbcsr_amd_bcsr_twin_apply", "dbcsr_amd_mm_set_canonical_product", "dbcsr_amd_multiply_symmetric_c",
     "dbcsr_amd_bcsr_desymmetrized", "dbcsr_amd_smm_last_kernel", "dbcsr_amd_multiply_symmetric_c_klimits",
+    "dbcsr_amd_bcsr_filter_apply_index", "dbcsr_amd_mm_set_filter_in_place",
 ]
 
 
@@ -132,6 +133,8 @@ def load_library(lab=False):
     L.dbcsr_amd_mm_symbolic_filtered.argtypes = [vp, i32, C.c_double, C.c_double, BP, BP, BP, i32, vp, C.POINTER(MmCounts), vp]
     L.dbcsr_amd_bcsr_filter_count.argtypes = [vp, i32, BP, C.c_double, vp, C.POINTER(i64), C.POINTER(i64), vp]
     L.dbcsr_amd_bcsr_filter_apply.argtypes = [vp, i32, BP, BP, vp]
+    L.dbcsr_amd_bcsr_filter_apply_index.argtypes = [vp, BP, BP, vp]
+    L.dbcsr_amd_mm_set_filter_in_place.argtypes = [vp, i32]
     L.dbcsr_amd_bcsr_crop_count.argtypes = [vp, i32, BP, i64, i64, i64, i64, vp, C.POINTER(i64), C.POINTER(i64), vp]
     L.dbcsr_amd_bcsr_crop_apply.argtypes = [vp, i32, BP, BP, vp]
     L.dbcsr_amd_bcsr_scale_window.argtypes = [vp, i32, BP, C.c_double, i64, i64, i64, i64, vp]

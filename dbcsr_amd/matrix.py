@@ -52,7 +52,7 @@ def _serial(t):
 
 
 class DbcsrMatrix:
-    def __init__(self, row_blk_size, col_blk_size, row_p, col_i, blk_p, data, name="", symmetry="N"):
+    def __init__(self, row_blk_size, col_blk_size, row_p, col_i, blk_p, data, name="", symmetry="N", nze=None):
         self._generation = 0   # bumped whenever the library is handed this matrix as a destination (it writes the index arrays)
         self.row_blk_size, self.col_blk_size = row_blk_size, col_blk_size
         self.row_p, self.col_i, self.blk_p, self.data = row_p, col_i, blk_p, data
@@ -60,6 +60,8 @@ class DbcsrMatrix:
         # matrix_type of the reference (src/core/dbcsr_types.F): 'N' no symmetry, 'S' symmetric, 'A' antisymmetric -- the latter
         # two store one block per symmetric pair
         self.symmetry = symmetry
+        # number of elements the index refers to when that is not the whole data area (see nze); None: all of it
+        self._nze = None if nze is None else int(nze)
 
     # -- construction -------------------------------------------------------
     @classmethod
@@ -88,6 +90,27 @@ class DbcsrMatrix:
     @property
     def nblks(self):
         return int(self.col_i.numel())
+
+    @property
+    def nze(self):
+        """Number of elements the index refers to.  For a packed matrix (blk_p = running sum of the block sizes: every matrix this
+        library makes unless it is asked otherwise) that is the whole data area.  The result of an in-place filter
+        (MultiplyEngine.filtered(..., in_place=True)) keeps the product's data area and names fewer elements of it."""
+        return int(self.data.numel()) if self._nze is None else self._nze
+
+    @nze.setter
+    def nze(self, value):
+        self._nze = None if value is None else int(value)
+
+    @property
+    def packed(self):
+        """The index refers to every element of the data area (no holes left by dropped blocks)."""
+        return self.nze == int(self.data.numel())
+
+    def adopt(self, other):
+        """Takes over other's index arrays, data area and element count (the sizes stay): how a multiply hands its result to matrix_c."""
+        self.row_p, self.col_i, self.blk_p, self.data = other.row_p, other.col_i, other.blk_p, other.data
+        self._nze = other._nze
 
     @property
     def dtype(self):
@@ -122,4 +145,4 @@ class DbcsrMatrix:
 
     def copy(self):
         return DbcsrMatrix(self.row_blk_size, self.col_blk_size, self.row_p.clone(), self.col_i.clone(), self.blk_p.clone(),
-                           self.data.clone(), self.name)
+                           self.data.clone(), self.name, nze=self._nze)

@@ -31,6 +31,9 @@ class MultiplyEngine:
         rc = self.L.dbcsr_amd_mm_create(C.byref(self.h))
         if rc != 0:
             raise RuntimeError("dbcsr_amd_mm_create failed (%d)" % rc)
+        # the final filter of multiply_local drops blocks by rewriting C's index only (filtered(..., in_place=True)): the result is
+        # not packed.  set_filter_in_place() also tells the handle, for the one-call C path (dbcsr_amd_multiply).
+        self.filter_in_place = False
 
     def close(self):
         if self.h:
@@ -47,7 +50,8 @@ class MultiplyEngine:
     def transposed(self, M, stream=None):
         st = StreamHandle(stream)
         out = DbcsrMatrix(M.col_blk_size, M.row_blk_size, torch.empty(M.nblkcols + 1, dtype=torch.int32, device=M.data.device),
-                          torch.empty_like(M.col_i), torch.empty_like(M.blk_p), torch.empty_like(M.data), M.name + "^T")
+                          torch.empty_like(M.col_i), torch.empty_like(M.blk_p),
+                          torch.empty(M.nze, dtype=M.dtype, device=M.data.device), M.name + "^T")   # (the transpose is written packed)
         src, dst = M.desc(), out.desc(out=True)
         rc = self.L.dbcsr_amd_bcsr_transpose(self.h, M.dtype_code, C.byref(src), C.byref(dst), st.ptr)
         if rc != 0:
@@ -187,6 +191,9 @@ class MultiplyEngine:
 
     def accumulate(self, alpha, A, B, Cacc, stream=None):
         """Cacc += alpha*A*B restricted to Cacc's pattern, in place; returns counts of this pass."""
+        if not Cacc.packed:
+            # the numeric phase rewrites c_out->blk_p to the packed offsets (include/dbcsr_amd_mm.h): in place that needs a packed C_in
+            raise ValueError("accumulate: Cacc is not packed (the result of an in-place filter); pack it first with cropped(Cacc)")
         st = StreamHandle(stream)
         a, b, c = A.desc(), B.desc(), Cacc.desc()
         row_p = torch.empty(Cacc.nblkrows + 1, dtype=torch.int32, device=Cacc.row_p.device)
@@ -220,8 +227,10 @@ class MultiplyEngine:
             raise RuntimeError("dbcsr_amd_mm_numeric failed (%d)" % rc)
         return out
 
-    def filtered(self, M, eps, stream=None):
-        """Copy of M without the blocks whose squared Frobenius norm is below eps^2 (final filter of a multiply)."""
+    def filtered(self, M, eps, stream=None, in_place=False):
+        """M without the blocks whose squared Frobenius norm is below eps^2 (final filter of a multiply): a packed copy, or with
+        in_place=True a matrix that shares M.data and has new row_p / col_i / blk_p (kept blocks stay where they are, nze counts
+        them; cropped(result) packs it).  M itself when nothing falls below eps."""
         st = StreamHandle(stream)
         dev = M.row_p.device
         src = M.desc()
@@ -233,6 +242,14 @@ class MultiplyEngine:
             raise RuntimeError("dbcsr_amd_bcsr_filter_count failed (%d)" % rc)
         if nb.value == M.nblks:   # nothing falls below the threshold: no second copy of the matrix
             return M
+        if in_place:
+            out = DbcsrMatrix(M.row_blk_size, M.col_blk_size, row_p, torch.empty(nb.value, dtype=torch.int32, device=dev),
+                              torch.empty(nb.value, dtype=torch.int64, device=dev), M.data, M.name, nze=nz.value)
+            dst = out.desc(out=True)
+            rc = self.L.dbcsr_amd_bcsr_filter_apply_index(self.h, C.byref(src), C.byref(dst), st.ptr)
+            if rc != 0:
+                raise RuntimeError("dbcsr_amd_bcsr_filter_apply_index failed (%d)" % rc)
+            return out
         out = DbcsrMatrix(M.row_blk_size, M.col_blk_size, row_p, torch.empty(nb.value, dtype=torch.int32, device=dev),
                           torch.empty(nb.value, dtype=torch.int64, device=dev), torch.empty(nz.value, dtype=M.dtype, device=dev), M.name)
         dst = out.desc(out=True)
@@ -240,6 +257,12 @@ class MultiplyEngine:
         if rc != 0:
             raise RuntimeError("dbcsr_amd_bcsr_filter_apply failed (%d)" % rc)
         return out
+
+    def set_filter_in_place(self, on=True):
+        """filter_in_place for this engine's multiply_local AND for the one-call C path on its handle (dbcsr_amd_mm_set_filter_in_place)."""
+        if self.L.dbcsr_amd_mm_set_filter_in_place(self.h, 1 if on else 0) != 0:
+            raise RuntimeError("dbcsr_amd_mm_set_filter_in_place failed")
+        self.filter_in_place = bool(on)
 
     def desymmetrized(self, M, stream=None):
         """Full matrix of a symmetric ('S') / antisymmetric ('A') operand (dbcsr_desymmetrize_deep, done by the reference while
@@ -318,7 +341,7 @@ class MultiplyEngine:
     def scaled_window(self, M, beta, row_bounds=None, col_bounds=None, stream=None):
         """dbcsr_scale(matrix, beta, limits) on a copy of M: only the elements inside the window are scaled."""
         st = StreamHandle(stream)
-        out = DbcsrMatrix(M.row_blk_size, M.col_blk_size, M.row_p, M.col_i, M.blk_p, M.data.clone(), M.name)
+        out = DbcsrMatrix(M.row_blk_size, M.col_blk_size, M.row_p, M.col_i, M.blk_p, M.data.clone(), M.name, nze=M._nze)   # (same index, same holes)
         r0, r1 = (-1, -1) if row_bounds is None else (int(row_bounds[0]), int(row_bounds[1]))
         c0, c1 = (-1, -1) if col_bounds is None else (int(col_bounds[0]), int(col_bounds[1]))
         d = out.desc(out=True)
@@ -347,14 +370,14 @@ class MultiplyEngine:
         forced = os.environ.get("DBCSR_AMD_MM_KCHUNKS")
         if forced:
             return max(1, int(forced))
-        row_bytes = A.data.numel() * A.data.element_size() / max(1, A.nblkrows)
+        row_bytes = A.nze * A.data.element_size() / max(1, A.nblkrows)   # (stored elements, not the size of the data area)
         if row_bytes <= self.KCHUNK_ROW_BYTES or A.nblkcols < 64:
             return 1
         fill_a = A.nblks / max(1.0, float(A.nblkrows) * A.nblkcols)
         fill_b = fill_a if B is None else B.nblks / max(1.0, float(B.nblkrows) * B.nblkcols)
         if A.nblkcols * fill_a * fill_b < self.KCHUNK_MIN_PRODUCTS:   # (expected products per C block)
             return 1
-        if A.data.numel() > 1024 * max(1, A.nblks):
+        if A.nze > 1024 * max(1, A.nblks):
             # blocks above 32 x 32 on average: the workgroup-per-C-block kernel (mm_numeric_f64_big.h) shares its operand slabs through LDS and
             # re-reading and re-writing C per pass costs more than the passes save (72^3 at 30 % fill, 16384^2: 21.5 ms in one pass against
             # 25.5 ms in three, gpurun_out/r05_s02/large_blocks_after.jsonl)
@@ -481,7 +504,7 @@ class MultiplyEngine:
             raise RuntimeError("dbcsr_amd_mm_numeric failed (%d)" % rc)
         self.last_launch_flop, self.last_kchunks = counts.flop, 1
         if filter_eps and filter_eps > 0 and not retain_sparsity:  # dbcsr_mm_multrec.F:373-383
-            out = self.filtered(out, filter_eps, stream=stream)
+            out = self.filtered(out, filter_eps, stream=stream, in_place=self.filter_in_place)
         return out, counts
 
 
@@ -522,7 +545,7 @@ def dbcsr_multiply(transa, transb, alpha, matrix_a, matrix_b, beta, matrix_c, fi
         finally:
             E.set_canonical_product(False)
         up = E.twin_moved(canon, 2, c_symm)
-        matrix_c.row_p, matrix_c.col_i, matrix_c.blk_p, matrix_c.data = up.row_p, up.col_i, up.blk_p, up.data
+        matrix_c.adopt(up)
         return counts
     matrix_a, matrix_b = E.desymmetrized(matrix_a), E.desymmetrized(matrix_b)
     A = E.transposed(matrix_a) if transa != "N" else matrix_a
@@ -564,7 +587,7 @@ def dbcsr_multiply(transa, transb, alpha, matrix_a, matrix_b, beta, matrix_c, fi
             matrix_in = E.scaled_window(matrix_c, beta, rb, cb)
         beta_eff = 1.0
     out, counts = E.multiply_local(alpha, A, B, beta_eff, matrix_in, retain_sparsity=retain_sparsity, filter_eps=filter_eps or 0.0)
-    matrix_c.row_p, matrix_c.col_i, matrix_c.blk_p, matrix_c.data = out.row_p, out.col_i, out.blk_p, out.data
+    matrix_c.adopt(out)   # (with the engine's filter_in_place the result may be unpacked: nze travels with the arrays)
     if flop is not None:
         flop[:] = [counts.flop]
     return counts

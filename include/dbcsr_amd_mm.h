@@ -88,6 +88,24 @@ int dbcsr_amd_bcsr_filter_count(void* handle, libsmm_acc_data_t datatype, const 
   int64_t* new_nblks, int64_t* new_nze, void* stream);
 int dbcsr_amd_bcsr_filter_apply(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, dbcsr_amd_bcsr* dst, void* stream);
 
+/* Index-only form of dbcsr_amd_bcsr_filter_apply, after dbcsr_amd_bcsr_filter_count on the same handle and src:
+ * dst->row_p = the new_row_p of the count, dst->col_i / dst->blk_p caller-allocated [new_nblks], dst->data MUST be src->data
+ * (anything else: -1; so is a call without a count before it, or with a src whose nblks is not the counted one).  No element is
+ * moved: kept blocks keep their offsets, the dropped blocks' space stays allocated and unreferenced.  Works for real_8 and real_4
+ * alike (no datatype argument: no element is touched).
+ * What comes back is an UNPACKED matrix: blk_p is strictly increasing but no longer the running sum of the block sizes, and the
+ * index refers to new_nze elements of a larger data area.  Everything that reaches a block through blk_p takes it (operands A and
+ * B, C_in out of place, transpose, desymmetrize / twin, crop, scale_window, checksum).  The one rule it brings: it must not be the
+ * aliased c_in / c_out of an in-place dbcsr_amd_mm_numeric (see there: that needs a packed C_in).  A packed copy needs no function
+ * of its own: dbcsr_amd_bcsr_crop_count / _apply with all four bounds negative is a packing copy, and the only thing besides
+ * releasing the matrix that gives the dropped blocks' memory back.
+ * dbcsr_amd_mm_set_filter_in_place(handle, 1): the final filter inside dbcsr_amd_multiply (and dbcsr_amd_multiply_symmetric_c /
+ * _klimits, which call it) uses this form: c_out then owns the product's data area together with the new index arrays (the
+ * product's own index arrays are freed before the call returns), and dbcsr_amd_bcsr_release frees it as any other result.
+ * 0 (the default) switches back to the copying form. */
+int dbcsr_amd_bcsr_filter_apply_index(void* handle, const dbcsr_amd_bcsr* src, dbcsr_amd_bcsr* dst, void* stream);
+int dbcsr_amd_mm_set_filter_in_place(void* handle, int on);
+
 /* Submatrix limits of dbcsr_multiply (first_row ... last_k, src/mm/dbcsr_mm.F:631-709): dbcsr_crop_matrix
  * (src/ops/dbcsr_operations.F:1652-1833) keeps the blocks that intersect the window [row_lo, row_hi] x [col_lo, col_hi]
  * (0-based inclusive ELEMENT indices of the full matrix; a negative bound = no bound) and clears the parts of the
