@@ -3,6 +3,7 @@
 // mm_workspace.h, mm_symbolic.h, mm_numeric_f64.h, mm_numeric_f32.h, mm_aux.h.
 #ifndef DBCSR_AMD_MM_AUX_H
 #define DBCSR_AMD_MM_AUX_H
+#include "mm_epilogue.h"  // wave_sum
 
 namespace dbcsr_amd {
 
@@ -32,11 +33,8 @@ __global__ void __launch_bounds__(256) checksum_blocks(const int* __restrict__ r
       sp += x * log(fabs((double)(roff[row] + r + 1) * (double)(coff[c] + cc + 1)));
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    s2 += __shfl_down(s2, off, 64);
-    sp += __shfl_down(sp, off, 64);
-  }
+  s2 = wave_sum(s2);
+  sp = wave_sum(sp);
   if (lane == 0) {
     row_sums[2 * row] = s2;
     row_sums[2 * row + 1] = sp;
@@ -309,8 +307,7 @@ __global__ void __launch_bounds__(256) filter_flags(const double* __restrict__ n
     blk_nze[b] = k ? rs[row] * cs[col_i[b]] : 0;
     cnt += k;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
+  cnt = wave_sum(cnt);
   if (lane == 0) row_keep[row] = cnt;
   (void)nblks;
 }
@@ -378,8 +375,7 @@ __global__ void __launch_bounds__(256) crop_flags(const int* __restrict__ row_p,
     blk_nze[b] = k ? m * n : 0;
     cnt += k;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
+  cnt = wave_sum(cnt);
   if (lane == 0) row_keep[row] = cnt;
 }
 

@@ -17,6 +17,7 @@
 #define DBCSR_AMD_MM_DMA_H
 
 #include "dma_lds.h"
+#include "mm_epilogue.h"
 
 namespace dbcsr_amd {
 
@@ -144,40 +145,10 @@ __device__ __forceinline__ void cblock_f64_dma(const Desc& d, const Entry* __res
     const Entry ep = e[p];
     if (ep.ks() != K) block_product_f64<MA, NC, false>(acc, a_data + ep.a_off(), b_data + ep.b_off(), M, N, ep.ks(), L);
   }
-  // C epilogue through LDS (slot 0; every DMA has landed): the block leaves as stored, in whole 1 KiB pieces, streaming hint
-  constexpr int CC = (M * N * 8 + 1023) / 1024;
-  static_assert(CC * 1024 <= S * SLOT, "C staging must fit the ring");
-  double* lds_c = reinterpret_cast<double*>(ring);
-#pragma unroll
-  for (int a = 0; a < MA; ++a)
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int row = 8 * a + L.rowd, col = 8 * c + L.coll;
-      if (row < M && col < N) lds_c[row + M * col] = alpha * acc[a][c];
-    }
-  const bool has_in = d.cin_off >= 0;
-  const __amdgpu_buffer_rsrc_t rsc = __builtin_amdgcn_make_buffer_rsrc((void*)(c_out + d.c_off), 0, M * N * 8, 0x00020000);
-  typedef double f64x2 __attribute__((ext_vector_type(2)));
-  if (has_in) {
-    const __amdgpu_buffer_rsrc_t rsi = __builtin_amdgcn_make_buffer_rsrc((void*)(c_in + d.cin_off), 0, M * N * 8, 0x00020000);
-    u32x4 ci[CC];
-#pragma unroll
-    for (int c = 0; c < CC; ++c) ci[c] = __builtin_amdgcn_raw_buffer_load_b128(rsi, voff, c * 1024, 0);
-#pragma unroll
-    for (int c = 0; c < CC; ++c) {
-      f64x2 v = *reinterpret_cast<const f64x2*>(ring + c * 1024 + voff);
-      const f64x2 w = __builtin_bit_cast(f64x2, ci[c]);
-      v[0] += beta * w[0];
-      v[1] += beta * w[1];
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsc, voff + c * 1024, 0, 2);
-    }
-  } else {
-#pragma unroll
-    for (int c = 0; c < CC; ++c) {
-      const u32x4 v = *reinterpret_cast<const u32x4*>(ring + c * 1024 + voff);
-      __builtin_amdgcn_raw_buffer_store_b128(v, rsc, voff + c * 1024, 0, 2);
-    }
-  }
+  // C epilogue through LDS (mm_epilogue.h), in slot 0: every DMA has landed
+  static_assert(((M * N * 8 + 1023) / 1024) * 1024 <= S * SLOT, "C staging must fit the ring");
+  stage_c_block<M, N>(reinterpret_cast<double*>(ring), acc, alpha, L);
+  store_c_block<M, N>(ring, c_out + d.c_off, d.cin_off >= 0 ? c_in + d.cin_off : nullptr, beta, lane, nullptr);
 }
 
 template <int M, int N, int K, int S>

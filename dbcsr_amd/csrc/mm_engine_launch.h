@@ -19,8 +19,7 @@ __global__ void __launch_bounds__(256) block_norms_other_sizes(const Desc* __res
   const double* x = c_data + d.c_off;
   double ss = 0.0;
   for (int e = lane; e < d.m * d.n; e += 64) ss += x[e] * x[e];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) ss += __shfl_down(ss, off, 64);
+  ss = wave_sum(ss);
   if (lane == 0) norms[cb] = ss;
 }
 
@@ -44,8 +43,7 @@ __global__ void __launch_bounds__(256) block_norms_unserved_classes(const Desc* 
   const double* x = c_data + d.c_off;
   double ss = 0.0;
   for (int e = lane; e < d.m * d.n; e += 64) ss += x[e] * x[e];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) ss += __shfl_down(ss, off, 64);
+  ss = wave_sum(ss);
   if (lane == 0) norms[cb] = ss;
 }
 

@@ -19,6 +19,7 @@
 #define DBCSR_AMD_MM_EXACT_H
 #include "mm_types.h"
 #include "smm_core.h"
+#include "mm_epilogue.h"
 
 // Tuning switches (run-time compiled kernels take them from DBCSR_AMD_JIT_DEFS, e.g. "-DDBCSR_EXACT_ALL_PIECES=1"):
 //  DBCSR_EXACT_ALL_PIECES   1: every product issues the loads / LDS copies of the LARGEST inner size of the class (pieces past
@@ -38,6 +39,7 @@ namespace dbcsr_amd {
 
 template <int LD>
 struct Pitch {  // leading dimension in LDS (doubles) of a column-major block whose columns have LD elements
+                // (NOT the rule of cblock_f64_exact in mm_numeric_f64.h, which pads B columns of 8 and 24 too: different LDS layouts and timings)
   static constexpr int PAD = (LD % 16 == 0) ? 2 : 0;
   static constexpr int P = LD + PAD;
 };
@@ -263,75 +265,16 @@ __device__ __forceinline__ void cblock_f64_classes(const Desc& d, const Entry fi
   }
 
   const bool has_in = d.cin_off >= 0;
-  // the final block filter is known and the block is new (mm_numeric_f64.h: cblock_f64_exact): its norm from the accumulators; a block the filter will drop is
-  // neither staged nor written
+  // the announced final filter: a new block's norm from the accumulators; a block the filter will drop is neither staged nor written (mm_epilogue.h: acc_norm2)
   if (norm_out && drop_below > 0.0 && !has_in) {
-    double s2 = 0.0;
-#pragma unroll
-    for (int a = 0; a < MA; ++a)
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const int row = 8 * a + L.rowd, col = 8 * c + L.coll;
-        const double v = alpha * acc[a][c];
-        if (row < M && col < N) s2 += v * v;
-      }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s2 += __shfl_down(s2, off, 64);
-    s2 = __shfl(s2, 0, 64);
+    const double s2 = acc_norm2<M, N>(acc, alpha, L);
     if (lane == 0) *norm_out = s2;
     if (s2 < drop_below) return;
     norm_out = nullptr;   // (written)
   }
-  // C epilogue through LDS: the block leaves as stored, in whole 1 KiB pieces (16 B per lane), streaming hint
-  constexpr int CC = (M * N * 8 + 1023) / 1024;
-  double* lds_c = reinterpret_cast<double*>(lds);
-#pragma unroll
-  for (int a = 0; a < MA; ++a)
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int row = 8 * a + L.rowd, col = 8 * c + L.coll;
-      if (row < M && col < N) lds_c[row + M * col] = alpha * acc[a][c];
-    }
-  const __amdgpu_buffer_rsrc_t rsc = __builtin_amdgcn_make_buffer_rsrc((void*)(c_out + d.c_off), 0, M * N * 8, 0x00020000);
-  typedef double f64x2 __attribute__((ext_vector_type(2)));
-  double ss = 0.0;  // squared Frobenius norm of the stored block for the final filter of a filtered multiply: summed as the values leave
-  // (the stores below carry the piece offset in the vector / immediate offset, not in an SGPR soffset: see cblock_f64_exact in mm_numeric_f64.h -- the store-data hazard)
-  if (has_in) {
-    const __amdgpu_buffer_rsrc_t rsi = __builtin_amdgcn_make_buffer_rsrc((void*)(c_in + d.cin_off), 0, M * N * 8, 0x00020000);
-    u32x4 ci[CC];
-#pragma unroll
-    for (int c = 0; c < CC; ++c) ci[c] = __builtin_amdgcn_raw_buffer_load_b128(rsi, voff, c * 1024, 0);
-#pragma unroll
-    for (int c = 0; c < CC; ++c) {
-      f64x2 v = *reinterpret_cast<const f64x2*>(lds + c * 1024 + voff);
-      const f64x2 w = __builtin_bit_cast(f64x2, ci[c]);
-      v[0] += beta * w[0];
-      v[1] += beta * w[1];
-      if (norm_out) {
-        const int idx = c * 128 + 2 * lane;
-        if (idx < M * N) ss += v[0] * v[0];
-        if (idx + 1 < M * N) ss += v[1] * v[1];
-      }
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsc, voff + c * 1024, 0, 2);
-    }
-  } else {
-#pragma unroll
-    for (int c = 0; c < CC; ++c) {
-      const u32x4 v = *reinterpret_cast<const u32x4*>(lds + c * 1024 + voff);
-      if (norm_out) {
-        const f64x2 x = __builtin_bit_cast(f64x2, v);
-        const int idx = c * 128 + 2 * lane;
-        if (idx < M * N) ss += x[0] * x[0];
-        if (idx + 1 < M * N) ss += x[1] * x[1];
-      }
-      __builtin_amdgcn_raw_buffer_store_b128(v, rsc, voff + c * 1024, 0, 2);
-    }
-  }
-  if (norm_out) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) ss += __shfl_down(ss, off, 64);
-    if (lane == 0) *norm_out = ss;
-  }
+  // C epilogue through LDS (mm_epilogue.h)
+  stage_c_block<M, N>(reinterpret_cast<double*>(lds), acc, alpha, L);
+  store_c_block<M, N>(lds, c_out + d.c_off, has_in ? c_in + d.cin_off : nullptr, beta, lane, norm_out);
 }
 
 // one wave per C block; order[] holds the class's segment (per-XCD streams padded with -1, as for the other kernels)
@@ -583,36 +526,9 @@ __device__ __forceinline__ void mm_class_stream_body(const Desc* __restrict__ de
       const Entry ep = entries[d_ps + p];
       if (!in_set(ep.ks())) block_product_f64<MA, NC, false>(acc, a_data + ep.a_off(), b_data + ep.b_off(), M, N, ep.ks(), L);
     }
-    // C epilogue through LDS (the operands of the next product are still in registers, not in LDS)
-    constexpr int CC = (M * N * 8 + 1023) / 1024;
-    double* lds_c = reinterpret_cast<double*>(lds);
-#pragma unroll
-    for (int a = 0; a < MA; ++a)
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const int row = 8 * a + L.rowd, col = 8 * c + L.coll;
-        if (row < M && col < N) lds_c[row + M * col] = alpha * acc[a][c];
-      }
-    const bool has_in = d_cin_off >= 0;
-    const __amdgpu_buffer_rsrc_t rsc = __builtin_amdgcn_make_buffer_rsrc((void*)(c_out + d_c_off), 0, M * N * 8, 0x00020000);
-    typedef double f64x2 __attribute__((ext_vector_type(2)));
-    if (has_in) {
-      const __amdgpu_buffer_rsrc_t rsi = __builtin_amdgcn_make_buffer_rsrc((void*)(c_in + d_cin_off), 0, M * N * 8, 0x00020000);
-#pragma unroll
-      for (int c = 0; c < CC; ++c) {
-        f64x2 v = *reinterpret_cast<const f64x2*>(lds + c * 1024 + voff);
-        const f64x2 w = __builtin_bit_cast(f64x2, __builtin_amdgcn_raw_buffer_load_b128(rsi, voff, c * 1024, 0));
-        v[0] += beta * w[0];
-        v[1] += beta * w[1];
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsc, voff + c * 1024, 0, 2);
-      }
-    } else {
-#pragma unroll
-      for (int c = 0; c < CC; ++c) {
-        const u32x4 v = *reinterpret_cast<const u32x4*>(lds + c * 1024 + voff);
-        __builtin_amdgcn_raw_buffer_store_b128(v, rsc, voff + c * 1024, 0, 2);
-      }
-    }
+    // C epilogue through LDS (mm_epilogue.h; the operands of the next product are still in registers, not in LDS)
+    stage_c_block<M, N>(reinterpret_cast<double*>(lds), acc, alpha, L);
+    store_c_block<M, N>(lds, c_out + d_c_off, d_cin_off >= 0 ? c_in + d_cin_off : nullptr, beta, lane, nullptr);
   }
 }
 

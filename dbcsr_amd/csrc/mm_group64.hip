@@ -3,6 +3,7 @@
 // the same reason (Makefile).
 #include "mm_group64.h"
 #include "smm_core.h"
+#include "mm_epilogue.h"
 #include <type_traits>
 #include <cstdlib>
 
@@ -384,11 +385,7 @@ mm_numeric_f64_group(const Desc* __restrict__ descs, const Entry* __restrict__ e
       }
     }
   }
-  // the R C blocks leave through LDS in whole 1 KiB pieces with the streaming hint (as cblock_f64_exact); their descriptors and C_in
-  // blocks are requested together, ahead of the first block's turn
-  constexpr int CC = X::CC;
-  double* lds_c = reinterpret_cast<double*>(lds_a);
-  typedef double f64x2 __attribute__((ext_vector_type(2)));
+  // the R C blocks leave through LDS one after the other (mm_epilogue.h); their descriptors are requested together, ahead of the first block's turn
   Desc dr[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) dr[r] = descs[cbr[r] >= 0 ? cbr[r] : 0];
@@ -400,37 +397,8 @@ mm_numeric_f64_group(const Desc* __restrict__ descs, const Entry* __restrict__ e
     const int64_t cin_off = (int64_t)(((uint64_t)sgpr((uint32_t)((uint64_t)d.cin_off >> 32)) << 32) | sgpr((uint32_t)d.cin_off));
     const int pc = (int)sgpr((uint32_t)d.prod_cnt);
     if ((skip_empty & 1) && pc == 0) continue;
-    const bool has_in = cin_off >= 0;
-    const __amdgpu_buffer_rsrc_t rsc = __builtin_amdgcn_make_buffer_rsrc((void*)(c_out + c_off), 0, S * S * 8, 0x00020000);
-    u32x4 ci[CC];
-    if (has_in) {
-      const __amdgpu_buffer_rsrc_t rsi = __builtin_amdgcn_make_buffer_rsrc((void*)(c_in + cin_off), 0, S * S * 8, 0x00020000);
-#pragma unroll
-      for (int c = 0; c < CC; ++c) ci[c] = __builtin_amdgcn_raw_buffer_load_b128(rsi, voff, c * 1024, 0);
-    }
-#pragma unroll
-    for (int a = 0; a < MA; ++a)
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const int row = 8 * a + L.rowd, col = 8 * c + L.coll;
-        if (row < S && col < S) lds_c[row + S * col] = alpha * acc[r][a][c];
-      }
-    if (has_in) {
-#pragma unroll
-      for (int c = 0; c < CC; ++c) {
-        f64x2 v = *reinterpret_cast<const f64x2*>(lds_a + c * 1024 + voff);
-        const f64x2 w = __builtin_bit_cast(f64x2, ci[c]);
-        v[0] += beta * w[0];
-        v[1] += beta * w[1];
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsc, voff + c * 1024, 0, 2);
-      }
-    } else {
-#pragma unroll
-      for (int c = 0; c < CC; ++c) {
-        const u32x4 v = *reinterpret_cast<const u32x4*>(lds_a + c * 1024 + voff);
-        __builtin_amdgcn_raw_buffer_store_b128(v, rsc, voff + c * 1024, 0, 2);
-      }
-    }
+    stage_c_block<S, S>(reinterpret_cast<double*>(lds_a), acc[r], alpha, L);
+    store_c_block<S, S>(lds_a, c_out + c_off, cin_off >= 0 ? c_in + cin_off : nullptr, beta, lane, nullptr);
   }
 }
 

@@ -21,7 +21,7 @@
 namespace dbcsr_amd {
 namespace {
 
-#include "jit_sources.inc"  // kJitSrc_mm_types, kJitSrc_smm_core, kJitSrc_mm_exact, kJitSrc_smm_exact: the texts of the four headers
+#include "jit_sources.inc"  // kJitSrc_mm_types, kJitSrc_smm_core, kJitSrc_mm_epilogue, kJitSrc_mm_exact, kJitSrc_smm_exact: the texts of the five headers
 
 typedef struct _hiprtcProgram* rtc_program;
 struct Rtc {
@@ -83,10 +83,10 @@ int compile_and_load(const char* defs, const char* tu_name, const char* what, co
   Rtc& r = rtc();
   if (!r.ok) return -1;
   g_last_from_cache = false;
-  const char* hsrc[] = {kJitSrc_mm_types, kJitSrc_smm_core, kJitSrc_mm_exact, kJitSrc_smm_exact};
-  const char* hname[] = {"mm_types.h", "smm_core.h", "mm_exact.h", "smm_exact.h"};
+  const char* hsrc[] = {kJitSrc_mm_types, kJitSrc_smm_core, kJitSrc_mm_epilogue, kJitSrc_mm_exact, kJitSrc_smm_exact};
+  const char* hname[] = {"mm_types.h", "smm_core.h", "mm_epilogue.h", "mm_exact.h", "smm_exact.h"};
   rtc_program prog = nullptr;
-  if (r.CreateProgram(&prog, defs, tu_name, 4, hsrc, hname) != 0) return -1;
+  if (r.CreateProgram(&prog, defs, tu_name, (int)(sizeof hname / sizeof hname[0]), hsrc, hname) != 0) return -1;
   std::string arch = std::string("--offload-arch=") + prop.gcnArchName;
   // DBCSR_AMD_JIT_DEFS: extra -D switches for the kernel text (tuning experiments, see mm_exact.h), space separated
   std::vector<std::string> extra;
@@ -105,7 +105,7 @@ int compile_and_load(const char* defs, const char* tu_name, const char* what, co
   for (const std::string& t : extra) opts.push_back(t.c_str());
   // DBCSR_AMD_JIT_CACHE=<directory>: code objects kept across processes (the reference compiles every triplet again in every run, ~0.5 s each:
   // docs/guide/3-developer-guide/3-programming/2-accelerator-backend/2-libsmm_acc/2-just-in-time-compilation.md).  The file name is a hash of everything the
-  // code depends on: the kernel text (macros and the four headers), the options, the architecture, the compiler library's version.
+  // code depends on: the kernel text (macros and the five headers), the options, the architecture, the compiler library's version.
   std::string cache_file;
   if (const char* dir = getenv("DBCSR_AMD_JIT_CACHE")) {
     if (*dir) {

@@ -3,6 +3,7 @@
 // mm_workspace.h, mm_symbolic.h, mm_numeric_f64.h, mm_numeric_f32.h, mm_aux.h.
 #ifndef DBCSR_AMD_MM_NUMERIC_F64_H
 #define DBCSR_AMD_MM_NUMERIC_F64_H
+#include "mm_epilogue.h"  // wave_sum, acc_norm2, stage_c_block, store_c_block: how a C block leaves its wave
 
 namespace dbcsr_amd {
 
@@ -43,8 +44,7 @@ __device__ __forceinline__ void cblock_f64(const Desc& d, const Entry* __restric
     }
   // (one tile covers the whole block here: row0 = col0 = 0) the squared norm of the block as stored, for the final filter of a filtered multiply
   if (norm_out) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) ss += __shfl_down(ss, off, 64);
+    ss = wave_sum(ss);
     if ((threadIdx.x & 63) == 0) *norm_out = ss;
   }
 }
@@ -205,6 +205,7 @@ __device__ __forceinline__ void cblock_f64_exact(const Desc& d, const Entry firs
   // (B columns of 24 doubles too: a stride of 192 bytes leaves 4 distinct bank groups for 8 columns, 2-way conflicts)
   // (23 x 23: columns of 46 dwords leave one pair of banks shared by two of the eight columns of a B fragment read; reading at a conflict-free pitch of
   // 25 -- timing only, session r06_20 -- gave 19.20 -> 19.04 ms on config 2: not worth staging B in 8-byte granules)
+  // (NOT the rule of Pitch<> in mm_exact.h, which pads multiples of 16 only: the two give different LDS layouts and timings)
   constexpr int APAD = (M % 16 == 0) ? 2 : 0, BPAD = (K % 8 == 0) ? 2 : 0, AP = M + APAD, BP = K + BPAD;
   static_assert(APAD == 0 || M % 2 == 0, "a lane's 16-byte granule (two doubles) must not straddle two padded columns");
   static_assert(BPAD == 0 || K % 2 == 0, "a lane's 16-byte granule (two doubles) must not straddle two padded columns");
@@ -329,22 +330,9 @@ __device__ __forceinline__ void cblock_f64_exact(const Desc& d, const Entry firs
   if constexpr (VAR == 3 || VAR == 4) asm volatile("" ::"v"(touch));  // the keep-alive loads are loads the compiler must keep
   before_epilogue();
   const bool has_in = d.cin_off >= 0;
-  // A filtered multiply whose final block filter is known (dbcsr_amd_mm_expect_filter; drop_below = its eps^2): a NEW block (no C_in: the usual case of a sparse
-  // product) has its norm in the accumulators -- formed here, before anything touches LDS, and a block the filter is going to drop (||blk||^2 < eps^2: the double
-  // written to norm_out, the comparison of filter_flags) is neither staged nor written.  Nobody reads it.  (Blocks with C_in take the epilogue below as always.)
+  // the announced final filter: a new block's norm from the accumulators; a block the filter will drop is neither staged nor written (mm_epilogue.h: acc_norm2)
   if (norm_out && drop_below > 0.0 && !has_in && !(dbg & 8)) {
-    double s2 = 0.0;
-#pragma unroll
-    for (int a = 0; a < MA; ++a)
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const int row = 8 * a + L.rowd, col = 8 * c + L.coll;
-        const double v = alpha * acc[a][c];
-        if (row < M && col < N) s2 += v * v;
-      }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s2 += __shfl_down(s2, off, 64);
-    s2 = __shfl(s2, 0, 64);
+    const double s2 = acc_norm2<M, N>(acc, alpha, L);
     if (lane == 0) *norm_out = s2;
     if (s2 < drop_below) return;
     norm_out = nullptr;   // (written)
@@ -365,69 +353,9 @@ __device__ __forceinline__ void cblock_f64_exact(const Desc& d, const Entry firs
       }
     return;
   }
-  // C epilogue through LDS: the block is laid out as stored (column-major, contiguous) in the wave's staging area and
-  // leaves in whole 1 KiB pieces -- 16 B per lane, full cache lines except at the two ends of the block -- with the
-  // streaming hint, so that the 8.6 GB of C that config 2 writes do not push the A block-rows out of L2 / the B panel out
-  // of the Infinity Cache.  (Non-temporal on the scattered 8-byte stores doubled WRITE_SIZE: partial lines are not combined.)
-  constexpr int CC = (M * N * 8 + 1023) / 1024;
-  double* lds_c = reinterpret_cast<double*>(lds_a);
-#pragma unroll
-  for (int a = 0; a < MA; ++a)
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int row = 8 * a + L.rowd, col = 8 * c + L.coll;
-      if (row < M && col < N) lds_c[row + M * col] = alpha * acc[a][c];
-    }
-  const __amdgpu_buffer_rsrc_t rsc = __builtin_amdgcn_make_buffer_rsrc((void*)(c_out + d.c_off), 0, M * N * 8, 0x00020000);
-  typedef double f64x2 __attribute__((ext_vector_type(2)));
-  double ss = 0.0;  // squared Frobenius norm of the block as it is stored (filtered multiplies): summed as the values leave
-  // The 16-byte stores below carry their piece offset in the VECTOR / immediate offset, never in the scalar offset: a buffer store of more than 64 bits whose soffset is an
-  // SGPR is NOT covered by the compiler's store-data hazard rule (it assumes none), yet on gfx950 a VALU write to the data registers right behind such a store reaches the
-  // store: the class (9, 32) kernel returned 16 elements per block with the low dword 0x100 (the next instruction's constant) in 0.2 % of the blocks (round 6, session 56).
-  if (has_in) {
-    const __amdgpu_buffer_rsrc_t rsi = __builtin_amdgcn_make_buffer_rsrc((void*)(c_in + d.cin_off), 0, M * N * 8, 0x00020000);
-    u32x4 ci[CC];
-#pragma unroll
-    for (int c = 0; c < CC; ++c) ci[c] = __builtin_amdgcn_raw_buffer_load_b128(rsi, voff, c * 1024, 0);
-#pragma unroll
-    for (int c = 0; c < CC; ++c) {
-      f64x2 v = *reinterpret_cast<const f64x2*>(lds_a + c * 1024 + voff);
-      const f64x2 w = __builtin_bit_cast(f64x2, ci[c]);
-      v[0] += beta * w[0];
-      v[1] += beta * w[1];
-      if (norm_out) {  // (the final values go into the norm as they leave: no second pass over the slice)
-        const int idx = c * 128 + 2 * lane;
-        if (idx < M * N) ss += v[0] * v[0];
-        if (idx + 1 < M * N) ss += v[1] * v[1];
-      }
-      if (dbg & 16)
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsc, voff + c * 1024, 0, 0);
-      else
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsc, voff + c * 1024, 0, 2);
-    }
-  } else {
-#pragma unroll
-    for (int c = 0; c < CC; ++c) {
-      const u32x4 v = *reinterpret_cast<const u32x4*>(lds_a + c * 1024 + voff);
-      if (norm_out) {
-        const f64x2 x = __builtin_bit_cast(f64x2, v);
-        const int idx = c * 128 + 2 * lane;
-        if (idx < M * N) ss += x[0] * x[0];
-        if (idx + 1 < M * N) ss += x[1] * x[1];
-      }
-      if (dbg & 16)
-        __builtin_amdgcn_raw_buffer_store_b128(v, rsc, voff + c * 1024, 0, 0);
-      else
-        __builtin_amdgcn_raw_buffer_store_b128(v, rsc, voff + c * 1024, 0, 2);
-    }
-  }
-  // squared Frobenius norm of the block as it was stored (the final block filter of a filtered multiply reads it instead of C):
-  // the block still sits in the wave's LDS slice
-  if (norm_out) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) ss += __shfl_down(ss, off, 64);
-    if (lane == 0) *norm_out = ss;
-  }
+  // C epilogue through LDS (mm_epilogue.h), in the wave's staging area
+  stage_c_block<M, N>(reinterpret_cast<double*>(lds_a), acc, alpha, L);
+  store_c_block<M, N>(lds_a, c_out + d.c_off, has_in ? c_in + d.cin_off : nullptr, beta, lane, norm_out, !(dbg & 16));
 }
 
 // C blocks of exactly M x N take the exact-size path; every other block of the launch the generic one.

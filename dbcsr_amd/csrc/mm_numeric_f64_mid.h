@@ -18,6 +18,7 @@
 #define DBCSR_AMD_MM_NUMERIC_F64_MID_H
 
 #include <type_traits>
+#include "mm_epilogue.h"  // wave_sum; the rules of the C epilogue through LDS (store_c_block)
 
 namespace dbcsr_amd {
 
@@ -268,7 +269,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) mm
       k0 = k2;
     }
     double ss = 0.0;
-    // the final block filter announced (norms[nblk] = its eps^2; mm_numeric_f64.h: cblock_f64_exact): a new block's norm from the accumulators, and a block the
+    // the final block filter announced (norms[nblk] = its eps^2; mm_epilogue.h: acc_norm2): a new block's norm from the accumulators, and a block the
     // filter is going to drop is neither staged nor written
     if (norms && d.cin_off < 0) {
       const double drop_below = norms[nblk];
@@ -278,8 +279,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) mm
           const double v = alpha * sum;
           if (row < m && col < n) s2 += v * v;
         });
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s2 += __shfl_down(s2, off, 64);
+        s2 = wave_sum(s2);
         s2 = __shfl(s2, 0, 64);
         if (lane == 0) norms[cb_index] = s2;
         if (s2 < drop_below) return;
@@ -287,7 +287,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) mm
       }
     }
     if constexpr (RBX <= 8 && CBX <= 8) {
-      // C epilogue through LDS (as the exact-size kernels, mm_numeric_f64.h): the block is laid out as stored (column-major, contiguous) in the wave's
+      // C epilogue through LDS (store_c_block in mm_epilogue.h with run-time extents; its rules hold here: the piece offset of a 16-byte store stays in the
+      // vector / immediate offset -- the store-data hazard explained there): the block is laid out as stored (column-major, contiguous) in the wave's
       // slice -- up to 32 x 32: it fits the slabs' 9 KB -- and leaves in whole 1 KiB pieces, 16 bytes per lane, with the streaming hint.  These shapes
       // are the classes of a mixed-size multiply with FEW products per C block (config 3: 3.6), where C's traffic counts: 7.25 against 7.6 ms there.
       double* lds_c = reinterpret_cast<double*>(smem);
@@ -333,8 +334,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) mm
     }
     // squared Frobenius norm of the block as it was stored: the final block filter of a filtered multiply reads it instead of C (as the exact-size kernels leave it)
     if (norms) {
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) ss += __shfl_down(ss, off, 64);
+      ss = wave_sum(ss);
       if (lane == 0) norms[cb_index] = ss;
     }
   }

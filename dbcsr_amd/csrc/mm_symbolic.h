@@ -3,6 +3,7 @@
 // mm_workspace.h, mm_symbolic.h, mm_numeric_f64.h, mm_numeric_f32.h, mm_aux.h.
 #ifndef DBCSR_AMD_MM_SYMBOLIC_H
 #define DBCSR_AMD_MM_SYMBOLIC_H
+#include "mm_epilogue.h"  // wave_sum
 
 namespace dbcsr_amd {
 
@@ -107,8 +108,7 @@ __global__ void __launch_bounds__(256) count_products(const int* __restrict__ a_
   }
   // block reduce, one atomic per workgroup
   __shared__ unsigned long long red[4];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) flop += __shfl_down(flop, off, 64);
+  flop = wave_sum(flop);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = flop;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -203,8 +203,7 @@ __global__ void __launch_bounds__(256) bcsr_block_norms(const int* __restrict__ 
       const double x = scale * (double)d[e];
       s += x * x;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    s = wave_sum(s);
     if (lane == 0) {
       if (norms) norms[b] = (float)s;
       if (norms64) norms64[b] = s;
@@ -296,8 +295,7 @@ __global__ void __launch_bounds__(256) count_products_grid(const int* __restrict
     }
   }
   __shared__ unsigned long long red[4];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) flop += __shfl_down(flop, off, 64);
+  flop = wave_sum(flop);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = flop;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -425,8 +423,7 @@ __global__ void __launch_bounds__(256) count_products_rows(const int* __restrict
     }
   }
   __shared__ unsigned long long red[4];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) flop += __shfl_down(flop, off, 64);
+  flop = wave_sum(flop);
   if (lane == 0) red[threadIdx.x >> 6] = flop;
   __syncthreads();
   if (threadIdx.x == 0) {

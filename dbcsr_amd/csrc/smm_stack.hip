@@ -23,6 +23,7 @@
 #include "common.h"
 #include "mm_types.h"
 #include "smm_core.h"
+#include "mm_epilogue.h"          // wave_sum
 #include "mm_numeric_f64_big.h"   // slab geometry of the workgroup-per-C-block kernel (BIG_KSL, BIG_PB, big_*_bytes)
 #include "mm_numeric_f64_mid.h"   // BigSub: a wave's block covered in units of 4 x 4 (the one-wave slab kernels)
 #include "mm_jit.h"               // jit_stack_kernel: the exact-size kernel of smm_exact.h, compiled per (m, n, k) at run time
@@ -453,8 +454,7 @@ __global__ void __launch_bounds__(256) block_norms_f64(const double* __restrict_
   const int ne = nelems[b];
   double s = 0.0;
   for (int i = lane; i < ne; i += 64) s += p[i] * p[i];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+  s = wave_sum(s);
   if (lane == 0) norms[b] = (float)s;
 }
 
