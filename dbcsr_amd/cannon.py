@@ -301,6 +301,8 @@ class CannonMultiply:
     def __init__(self, M=0, N=0, K=0, sparsities=(0, 0, 0), mix=(1, 1), dtype=torch.float64, engine=None, device=None, grid=None,
                  mix_n=None, mix_k=None, mode="gather", local_first=True, matrices=None, transport="torch", distributed=None,
                  col_chunks=8, share_comm_with=None):
+        if dtype.is_complex or (matrices is not None and any(np.iscomplexobj(m.data) for m in matrices)):
+            raise TypeError("CannonMultiply: complex data is not offered by the distributed multiply (one rank: dbcsr_multiply)")
         # transport: "torch" = torch.distributed point-to-point (RCCL under the nccl backend, gloo on CPU);
         #            "native" = the C-ABI exchange of include/dbcsr_amd_comm.h (RCCL group on a dedicated HIP stream);
         #            "auto"   = native when it can be set up (GPU tensors, more than one rank), else torch

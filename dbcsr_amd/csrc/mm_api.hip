@@ -20,7 +20,7 @@ using namespace dbcsr_amd;
 
 namespace {
 
-size_t elem_size(libsmm_acc_data_t dt) { return dt == dbcsr_type_real_8 ? 8 : 4; }
+size_t elem_size(libsmm_acc_data_t dt) { return dt == dbcsr_type_complex_8 ? 16 : dt == dbcsr_type_real_8 ? 8 : 4; }
 
 // a BCSR matrix whose four arrays were allocated here
 struct Owned {
@@ -89,7 +89,7 @@ int crop(void* h, libsmm_acc_data_t dt, const dbcsr_amd_bcsr* src, int64_t r0, i
   return dbcsr_amd_bcsr_crop_apply(h, dt, src, &dst.m, stream);
 }
 
-int transposed(void* h, libsmm_acc_data_t dt, const dbcsr_amd_bcsr* src, Owned& dst, void* stream) {
+int transposed(void* h, libsmm_acc_data_t dt, const dbcsr_amd_bcsr* src, Owned& dst, void* stream, bool conj = false) {
   // sizes of src: one counting pass over the whole matrix
   Owned probe;
   if (alloc_row_p(probe, src->nblkrows)) return -1;
@@ -97,7 +97,7 @@ int transposed(void* h, libsmm_acc_data_t dt, const dbcsr_amd_bcsr* src, Owned& 
   int rc = dbcsr_amd_bcsr_crop_count(h, dt, src, -1, -1, -1, -1, probe.m.row_p, &nb, &nz, stream);
   if (rc) return rc;
   if (alloc_arrays(dst, src->nblkcols, src->nblkrows, src->col_blk_size, src->row_blk_size, nb, nz, elem_size(dt), true)) return -1;
-  return dbcsr_amd_bcsr_transpose(h, dt, src, &dst.m, stream);
+  return conj ? dbcsr_amd_bcsr_transpose_conj(h, dt, src, &dst.m, stream) : dbcsr_amd_bcsr_transpose(h, dt, src, &dst.m, stream);
 }
 
 
@@ -141,10 +141,13 @@ int empty_like(const dbcsr_amd_bcsr* c, Owned& e, hipStream_t st) {
   return 0;
 }
 
-int symbolic_numeric(void* h, libsmm_acc_data_t dt, double alpha, const dbcsr_amd_bcsr* a, const dbcsr_amd_bcsr* b, double beta,
+// (alpha, beta: (re, im); real data reads the real parts only and takes the entries with real scalars, as it always did)
+int symbolic_numeric(void* h, libsmm_acc_data_t dt, const double alpha[2], const dbcsr_amd_bcsr* a, const dbcsr_amd_bcsr* b, const double beta[2],
                      const dbcsr_amd_bcsr* c_in, int retain, double eps, Owned& out, dbcsr_amd_mm_counts* counts, void* stream) {
+  const bool cplx = dt == dbcsr_type_complex_8;
   if (alloc_row_p(out, c_in->nblkrows)) return -1;
-  int rc = dbcsr_amd_mm_symbolic_filtered(h, dt, alpha, eps, a, b, c_in, retain, out.m.row_p, counts, stream);
+  // (the on-the-fly filter's rule uses ||alpha * B||: complex data hands it |alpha|)
+  int rc = dbcsr_amd_mm_symbolic_filtered(h, dt, cplx ? std::hypot(alpha[0], alpha[1]) : alpha[0], eps, a, b, c_in, retain, out.m.row_p, counts, stream);
   if (rc) return rc;
   if (alloc_arrays(out, c_in->nblkrows, c_in->nblkcols, c_in->row_blk_size, c_in->col_blk_size, counts->c_nblks, counts->c_nze, elem_size(dt),
                    false))
@@ -155,7 +158,8 @@ int symbolic_numeric(void* h, libsmm_acc_data_t dt, double alpha, const dbcsr_am
     const bool off = sw && atoi(sw) == 0;
     if (!off) dbcsr_amd_mm_expect_filter(h, eps);
   }
-  return dbcsr_amd_mm_numeric(h, dt, alpha, a, b, beta, c_in, &out.m, stream);
+  if (cplx) return dbcsr_amd_mm_numeric_z(h, alpha, a, b, beta, c_in, &out.m, stream);
+  return dbcsr_amd_mm_numeric(h, dt, alpha[0], a, b, beta[0], c_in, &out.m, stream);
 }
 
 // L2 blocking over k (see MultiplyEngine.multiply_local in dbcsr_amd/multiply.py for the measurements): when A's average block
@@ -163,6 +167,7 @@ int symbolic_numeric(void* h, libsmm_acc_data_t dt, double alpha, const dbcsr_am
 // operands (C's final structure, C = beta*C_in on it) followed by passes over k ranges that accumulate in place.
 int k_passes(void* h, libsmm_acc_data_t dt, const dbcsr_amd_bcsr* a, const dbcsr_amd_bcsr* b, double filter_eps, void* stream) {
   if (filter_eps > 0.0) return 1;  // the on-the-fly filter counts the blocks of a whole A row
+  if (dt == dbcsr_type_complex_8) return 1;   // complex multiplies run in one pass
   if (const char* f = getenv("DBCSR_AMD_MM_KCHUNKS")) return atoi(f) > 1 ? atoi(f) : 1;
   if (a->nblkcols < 64 || a->nblkrows < 1) return 1;
   // The probe below runs on the engine and costs it its plan (it shares the symbolic phase's work areas): a loop that multiplies the
@@ -264,13 +269,17 @@ int dbcsr_amd_bcsr_release(dbcsr_amd_bcsr* m) {
   return 0;
 }
 
-int dbcsr_amd_multiply(void* handle, char transa, char transb, libsmm_acc_data_t datatype, double alpha, const dbcsr_amd_bcsr* matrix_a,
-                       const dbcsr_amd_bcsr* matrix_b, double beta, const dbcsr_amd_bcsr* matrix_c, const int64_t* limits, int retain_sparsity,
-                       double filter_eps, dbcsr_amd_bcsr* c_out, int64_t* flop, void* stream) {
+static int multiply_any(void* handle, char transa, char transb, libsmm_acc_data_t datatype, const double alpha_z[2], const dbcsr_amd_bcsr* matrix_a,
+                        const dbcsr_amd_bcsr* matrix_b, const double beta_z[2], const dbcsr_amd_bcsr* matrix_c, const int64_t* limits,
+                        int retain_sparsity, double filter_eps, dbcsr_amd_bcsr* c_out, int64_t* flop, void* stream) {
   if (!handle || !matrix_a || !matrix_b || !matrix_c || !c_out) return -1;
-  if (datatype != dbcsr_type_real_8 && datatype != dbcsr_type_real_4) return -10;
+  if (datatype != dbcsr_type_real_8 && datatype != dbcsr_type_real_4 && datatype != dbcsr_type_complex_8) return -10;
+  const bool cplx = datatype == dbcsr_type_complex_8;
+  const double alpha = alpha_z[0], beta = beta_z[0];
+  const bool beta_is_zero = beta == 0.0 && (!cplx || beta_z[1] == 0.0), beta_is_one = beta == 1.0 && (!cplx || beta_z[1] == 0.0);
   auto is_n = [](char t) { return t == 'N' || t == 'n'; };
-  auto is_t = [](char t) { return t == 'T' || t == 't' || t == 'C' || t == 'c'; };  // real data: 'C' == 'T'
+  auto is_c = [](char t) { return t == 'C' || t == 'c'; };
+  auto is_t = [](char t) { return t == 'T' || t == 't' || t == 'C' || t == 'c'; };  // real data: 'C' == 'T'; complex data: 'C' conjugates
   if ((!is_n(transa) && !is_t(transa)) || (!is_n(transb) && !is_t(transb))) {
     fprintf(stderr, "dbcsr_amd_multiply: invalid transpose flag\n");
     return -1;
@@ -283,11 +292,11 @@ int dbcsr_amd_multiply(void* handle, char transa, char transb, libsmm_acc_data_t
   const dbcsr_amd_bcsr* A = matrix_a;
   const dbcsr_amd_bcsr* B = matrix_b;
   if (is_t(transa)) {
-    if ((rc = transposed(handle, datatype, matrix_a, ta, stream))) return rc;
+    if ((rc = transposed(handle, datatype, matrix_a, ta, stream, cplx && is_c(transa)))) return rc;
     A = &ta.m;
   }
   if (is_t(transb)) {
-    if ((rc = transposed(handle, datatype, matrix_b, tb, stream))) return rc;
+    if ((rc = transposed(handle, datatype, matrix_b, tb, stream, cplx && is_c(transb)))) return rc;
     B = &tb.m;
   }
   if (A->nblkcols != B->nblkrows || A->nblkrows != matrix_c->nblkrows || B->nblkcols != matrix_c->nblkcols) {
@@ -298,7 +307,8 @@ int dbcsr_amd_multiply(void* handle, char transa, char transb, libsmm_acc_data_t
   // step are the reference's (src/mm/dbcsr_mm.F:631-692): an invalid limit is an error there (DBCSR_ABORT), never clamped.
   Owned ca, cb, cc, cempty;
   const dbcsr_amd_bcsr* Cin = matrix_c;
-  double beta_eff = beta;
+  double beta_eff[2] = {beta, cplx ? beta_z[1] : 0.0};
+  const double alpha_eff[2] = {alpha, cplx ? alpha_z[1] : 0.0};
   bool limited = false;
   if (limits)
     for (int i = 0; i < 6; ++i) limited = limited || limits[i] != 0;
@@ -328,11 +338,11 @@ int dbcsr_amd_multiply(void* handle, char transa, char transb, libsmm_acc_data_t
   }
   // Product data is retained when retain_sparsity, beta != 0, or the row / column window ends inside C (dbcsr_mm.F:695-704);
   // otherwise the old C is discarded before the multiplication: its blocks disappear and their values are never read.
-  const bool keep_product_data = retain_sparsity || beta != 0.0 || window_keeps;
+  const bool keep_product_data = retain_sparsity || !beta_is_zero || window_keeps;
   if (!keep_product_data) {
     if (empty_like(matrix_c, cempty, st)) return -1;
     Cin = &cempty.m;
-    beta_eff = 1.0;
+    beta_eff[0] = 1.0, beta_eff[1] = 0.0;
   }
   if (limited) {
     const int64_t r0 = f_row ? f_row - 1 : -1, r1 = l_row ? l_row - 1 : -1;
@@ -342,21 +352,23 @@ int dbcsr_amd_multiply(void* handle, char transa, char transb, libsmm_acc_data_t
     if ((rc = crop(handle, datatype, B, k0, k1, c0, c1, cb, nullptr, stream))) return rc;
     A = &ca.m;
     B = &cb.m;
-    if (beta != 1.0 && keep_product_data) {  // dbcsr_scale(matrix_c, beta, limits): on a copy, the caller's C stays as it is
+    if (!beta_is_one && keep_product_data) {  // dbcsr_scale(matrix_c, beta, limits): on a copy, the caller's C stays as it is
       int64_t nz = 0;
       if ((rc = crop(handle, datatype, matrix_c, -1, -1, -1, -1, cc, &nz, stream))) return rc;
-      if ((rc = dbcsr_amd_bcsr_scale_window(handle, datatype, &cc.m, beta, r0, r1, c0, c1, stream))) return rc;
+      if ((rc = cplx ? dbcsr_amd_bcsr_scale_window_z(handle, &cc.m, beta_z, r0, r1, c0, c1, stream)
+                     : dbcsr_amd_bcsr_scale_window(handle, datatype, &cc.m, beta, r0, r1, c0, c1, stream)))
+        return rc;
       Cin = &cc.m;
     }
-    beta_eff = 1.0;
+    beta_eff[0] = 1.0, beta_eff[1] = 0.0;
   }
   // the product (with the on-the-fly filter), then the final block filter
   Owned prod;
   dbcsr_amd_mm_counts counts;
   const int npass = k_passes(handle, datatype, A, B, filter_eps, stream);
   if (npass > 1) {
-    if ((rc = multiply_in_k_passes(handle, datatype, alpha, A, B, beta_eff, Cin, retain_sparsity, npass, prod, &counts, stream))) return rc;
-  } else if ((rc = symbolic_numeric(handle, datatype, alpha, A, B, beta_eff, Cin, retain_sparsity, filter_eps, prod, &counts, stream))) {
+    if ((rc = multiply_in_k_passes(handle, datatype, alpha, A, B, beta_eff[0], Cin, retain_sparsity, npass, prod, &counts, stream))) return rc;
+  } else if ((rc = symbolic_numeric(handle, datatype, alpha_eff, A, B, beta_eff, Cin, retain_sparsity, filter_eps, prod, &counts, stream))) {
     return rc;
   }
   if (flop) *flop = counts.flop;
@@ -392,6 +404,24 @@ int dbcsr_amd_multiply(void* handle, char transa, char transb, libsmm_acc_data_t
   c_out->col_blk_size = matrix_c->col_blk_size;
   result->live = false;  // ownership passes to the caller (dbcsr_amd_bcsr_release)
   return 0;
+}
+
+int dbcsr_amd_multiply(void* handle, char transa, char transb, libsmm_acc_data_t datatype, double alpha, const dbcsr_amd_bcsr* matrix_a,
+                       const dbcsr_amd_bcsr* matrix_b, double beta, const dbcsr_amd_bcsr* matrix_c, const int64_t* limits, int retain_sparsity,
+                       double filter_eps, dbcsr_amd_bcsr* c_out, int64_t* flop, void* stream) {
+  // complex_8 keeps its -10 HERE: hosts written against the real-only library probe this entry with the type code and real operands and take -10
+  // as "leave it to the reference path" (tests/test_gpu_native_multiply.py does); a complex multiply is asked for by name, dbcsr_amd_multiply_z
+  if (datatype != dbcsr_type_real_8 && datatype != dbcsr_type_real_4) return -10;
+  const double al[2] = {alpha, 0.0}, be[2] = {beta, 0.0};
+  return multiply_any(handle, transa, transb, datatype, al, matrix_a, matrix_b, be, matrix_c, limits, retain_sparsity, filter_eps, c_out, flop, stream);
+}
+
+int dbcsr_amd_multiply_z(void* handle, char transa, char transb, const double alpha[2], const dbcsr_amd_bcsr* matrix_a, const dbcsr_amd_bcsr* matrix_b,
+                         const double beta[2], const dbcsr_amd_bcsr* matrix_c, const int64_t* limits, int retain_sparsity, double filter_eps,
+                         dbcsr_amd_bcsr* c_out, int64_t* flop, void* stream) {
+  if (!alpha || !beta) return -1;
+  return multiply_any(handle, transa, transb, dbcsr_type_complex_8, alpha, matrix_a, matrix_b, beta, matrix_c, limits, retain_sparsity, filter_eps, c_out,
+                      flop, stream);
 }
 
 int dbcsr_amd_bcsr_desymmetrized(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, int antisymmetric, dbcsr_amd_bcsr* dst,

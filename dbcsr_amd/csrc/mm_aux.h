@@ -97,8 +97,9 @@ __global__ void __launch_bounds__(256) fill_random_f64(const int* __restrict__ r
                                                        const int64_t* __restrict__ blk_p, double* __restrict__ data,
                                                        const int* __restrict__ rs, const int* __restrict__ cs, int nbr, int nbc,
                                                        int counter, const int* __restrict__ row_gid, const int* __restrict__ col_gid,
-                                                       int nrow_global) {
-  // one wavefront per block row, lanes over the elements of each block
+                                                       int nrow_global, int elem_doubles) {
+  // one wavefront per block row, lanes over the elements of each block.  elem_doubles = 2: complex_8 data (zlarnv, idist = 1: a block's 2 m n doubles are
+  // the dlarnv stream of its seed, re, im, re, im, ...; `data` is the area viewed as doubles, blk_p counts complex elements)
   const int lane = threadIdx.x & 63;
   const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   if (row >= nbr) return;
@@ -107,10 +108,10 @@ __global__ void __launch_bounds__(256) fill_random_f64(const int* __restrict__ r
   const uint64_t a64 = pow48(A, 64);
   for (int b = row_p[row]; b < row_p[row + 1]; ++b) {
     const int c = col_i[b];
-    const int ne = rs[row] * cs[c];
+    const int ne = rs[row] * cs[c] * elem_doubles;
     const uint64_t seed = larnv_block_seed((row_gid ? row_gid[row] : row) + 1, nrow_global, (col_gid ? col_gid[c] : c) + 1, counter);
     uint64_t x = (seed * pow48(A, (uint64_t)lane + 1)) & mask;
-    double* d = data + blk_p[b];
+    double* d = data + blk_p[b] * elem_doubles;
     for (int e = lane; e < ne; e += 64) {
       d[e] = (double)x * (1.0 / 281474976710656.0);
       x = (x * a64) & mask;
@@ -166,8 +167,8 @@ __global__ void __launch_bounds__(256) fill_random_f32(const int* __restrict__ r
   }
 }
 
-// transpose: dst block (c, r) <- src block (r, c)^T
-template <typename T>
+// transpose: dst block (c, r) <- src block (r, c)^T (CONJ: its conjugate transpose)
+template <typename T, bool CONJ = false>
 __global__ void __launch_bounds__(256)
 transpose_fill(const int* __restrict__ s_row_p, const int* __restrict__ s_col_i, const int64_t* __restrict__ s_blk_p,
                const T* __restrict__ s_data, const int* __restrict__ s_rs, const int* __restrict__ s_cs, const uint32_t* __restrict__ t_bm,
@@ -193,7 +194,7 @@ transpose_fill(const int* __restrict__ s_row_p, const int* __restrict__ s_col_i,
     T* dst = t_data + toff;
     for (int e = lane; e < m * n; e += 64) {
       const int i = e % m, j = e / m;  // src(i, j) -> dst(j, i), dst is n x m
-      dst[j + (size_t)n * i] = src[e];
+      dst[j + (size_t)n * i] = CONJ ? conj_of(src[e]) : src[e];
     }
   }
 }

@@ -39,6 +39,11 @@ static inline bool f32_direct_has(int m, int n, int k) { const int s = m; return
 // mm_numeric_f64_big<TM, TN>: every pair of 2 ... 5
 static inline bool big_f64_has(int tm, int tn) { return tm >= 2 && tm <= 5 && tn >= 2 && tn <= 5; }
 static inline int big_tiles(int size) { return std::max(2, ((size + 7) / 8 + 1) / 2); }   // ... tiles of 8 per wave for blocks of that many rows / columns
+// mm_numeric_z64<MA, NC> (complex_8, mm_numeric_z64.h): every pair of 1 ... 4; tiles of 8 rows / columns of the instance that serves blocks of that size
+// (a dimension above 32 is covered in several tiles of 32), and the per-wave LDS slice: A's slab of 8 columns of 8 MA + 1 elements, B's 8 NC runs of 9
+static inline bool z64_has(int ma, int nc) { return ma >= 1 && ma <= 4 && nc >= 1 && nc <= 4; }
+static inline int z64_tiles(int size) { return std::max(1, (std::min(size, 32) + 7) / 8); }
+static inline constexpr int z64_slice_bytes(int ma, int nc) { return 8 * (8 * ma + 1) * 16 + 8 * nc * 9 * 16; }
 static inline bool mid_f64_has(int rb, int cb) {
 #define DBCSR_AMD_IS_(A_, B_) || (rb == A_ && cb == B_)
   return false DBCSR_AMD_MID_SHAPES(DBCSR_AMD_IS_);
@@ -82,6 +87,7 @@ struct SizeFacts {
   bool filter_active = false;   // the symbolic phase filtered on the fly (block norms of A and B are at hand)
   bool fp64 = true;
   int skip_empty = 0;           // in-place accumulation: C blocks without products are left untouched
+  bool cplx = false;            // complex_8 data: the one complex family serves every size (mm_numeric_z64.h)
 
   bool sizes_within(int s) const { return max_m <= s && max_k <= s && max_n <= s && min_m >= 1 && min_k >= 1 && min_n >= 1; }
   bool no_empty_dim() const { return min_m >= 1 && min_n >= 1 && min_k >= 1; }
@@ -175,7 +181,8 @@ static inline void choose_classes(SizeFacts* f, const Switches& sw, const int* h
 // ---- the numeric phase's choice ------------------------------------------------------------------------------------------------------------------------------
 enum class Family {
   f64_tiny, f64_small8, f64_mid, f64_classes, f64_hot, f64_pipe, f64_lds, f64_big, f64_generic, f32_classes, f32_direct, f32_hot, f32_lds, f32_generic,
-  f64_group, f64_tile, f64_band, f64_dma, f64_persistent, f32_group   // lab build only
+  f64_group, f64_tile, f64_band, f64_dma, f64_persistent, f32_group,  // lab build only
+  z64                                                                 // complex_8
 };
 
 struct NumericChoice {
@@ -230,7 +237,7 @@ static inline void choose_mid_shape(const SizeFacts& f, const Switches& sw, cons
   }
 }
 
-// The rules, in the order that decides: tiny -> small8 -> mid -> classes -> (lab: group, tile, band, dma, persistent) -> hot -> pipe / lds -> big -> generic
+// The rules, in the order that decides: complex data has its one family (z64); tiny -> small8 -> mid -> classes -> (lab: group, tile, band, dma, persistent) -> hot -> pipe / lds -> big -> generic
 // for fp64, classes -> (lab: group) -> direct -> hot -> lds -> generic for fp32.  `work` and `norms` are decided BEFORE the family, as the set-up steps they
 // stand for run before the launch.  Two reachable combinations set something up that the family then does not use, both kept as they always were:
 //  * a dominant cube of at most 8 (no exact-size instance) with the small-block kernel switched off builds work records and arms the norms, then runs the
@@ -253,6 +260,13 @@ static inline NumericChoice choose_numeric(const SizeFacts& f, const Switches& s
     snprintf(c.name, sizeof c.name, fmt, a, b, d, e);
     return c;
   };
+  if (f.cplx) {
+    // complex_8: one wave per C block in the instance of the multiply's largest block; no work records, no norms (the block filter computes them)
+    const int ma = z64_tiles(f.max_m), nc = z64_tiles(f.max_n);
+    c.lds_bytes = (size_t)c.ww * (size_t)z64_slice_bytes(ma, nc);
+    const unsigned waves = (unsigned)(f.order_len > 0 ? npos : nblk);
+    return pick(Family::z64, (waves + (unsigned)c.ww - 1) / (unsigned)c.ww, skip, "mm_numeric_z64<%d,%d>", ma, nc);
+  }
   if (!f.fp64) {
     if (!(small && sw.use_lds)) return pick(Family::f32_generic, quads, skip, "mm_numeric_f32");
     if (f.cls_mode) return pick(Family::f32_classes, per_wave, skip, "mm_numeric_f32_lds[per class segment]");

@@ -22,6 +22,7 @@
 //   mm_numeric_f64_lds<MAXT> / mm_numeric_f64_pipe<MAXT>   any sizes up to 32 (pipe: mixed sizes, few products per block)
 //   mm_numeric_f32_lds                                     fp32, any sizes up to 32
 //   mm_numeric_f64 / mm_numeric_f32                        blocks above 32 (32 x 32 tiles, fragments from global memory)
+//   mm_numeric_z64<MA,NC>                                  complex_8, any sizes: two accumulator sets, operands in slabs of 8 inner indices (mm_numeric_z64.h)
 // Around them: transpose, checksum, synthetic fill, norm filter, crop / window scale (submatrix limits).
 //
 // Files of this translation unit (included below, inside namespace dbcsr_amd unless they open it themselves):
@@ -47,6 +48,7 @@
 #include "common.h"
 #include "smm_core.h"
 #include "mm_types.h"
+#include "mm_complex.h"   // z64 and the per-element helpers of the type-generic kernels
 #include "mm_jit.h"
 
 #include "mm_workspace.h"
@@ -56,6 +58,7 @@
 #include "mm_numeric_f64_small.h"
 #include "mm_mid.h"   // the one-wave slab kernels of the blocks of 25 ... 40 (mm_numeric_f64_mid.h, mm_mid.hip)
 #include "mm_numeric_f32.h"
+#include "mm_numeric_z64.h"   // complex_8: one family for every block size
 #include "mm_aux.h"
 // The library comes in two builds (Makefile): the SHIPPING one holds what a multiply can run by itself -- the kernels listed above, their
 // symbolic phases, plan reuse -- and the LAB one (-DDBCSR_AMD_EXPERIMENTS, libdbcsr_acc_amd_lab.so) adds every dataflow and variant that
@@ -80,7 +83,7 @@ namespace dbcsr_amd {
 #include "mm_engine_lab.h"      // host side of the experimental dataflows
 #endif
 
-// ---- the numeric phase, step by step (dbcsr_amd_mm_numeric below) ----
+// ---- the numeric phase, step by step (numeric_phase below: dbcsr_amd_mm_numeric and dbcsr_amd_mm_numeric_z) ----
 
 // Product lists, C block descriptors and C's index.  Plan reuse: those of the previous multiply stand; C's index is copied from the saved one.
 static int build_product_lists(Engine* E, bool reuse, const dbcsr_amd_bcsr* a, const dbcsr_amd_bcsr* b, const dbcsr_amd_bcsr* c_in, dbcsr_amd_bcsr* c_out,
@@ -116,9 +119,9 @@ static int build_product_lists(Engine* E, bool reuse, const dbcsr_amd_bcsr* a, c
 
 template <typename T>
 static NumericArgs<T> numeric_args(Engine* E, hipStream_t st, const dbcsr_amd_bcsr* a, const dbcsr_amd_bcsr* b, const dbcsr_amd_bcsr* c_in,
-                                   const dbcsr_amd_bcsr* c_out, double alpha, double beta, const Work* work, double* norms, bool reuse) {
+                                   const dbcsr_amd_bcsr* c_out, T alpha, T beta, const Work* work, double* norms, bool reuse) {
   return NumericArgs<T>{st, E->descs.p, E->facts.c_nblks, E->entries.p, static_cast<const T*>(a->data), static_cast<const T*>(b->data),
-                        static_cast<T*>(c_out->data), static_cast<const T*>(c_in->data), (T)alpha, (T)beta, E->facts.skip_empty, E->order.p, work, norms,
+                        static_cast<T*>(c_out->data), static_cast<const T*>(c_in->data), alpha, beta, E->facts.skip_empty, E->order.p, work, norms,
                         a, b, c_out, reuse};
 }
 
@@ -242,6 +245,18 @@ static int launch_f32(Engine* E, const NumericChoice& c, const NumericArgs<float
   }
 }
 
+// complex_8: the one family (mm_numeric_z64.h)
+static int launch_z64_family(Engine* E, const NumericChoice& c, const NumericArgs<z64>& p) {
+  const SizeFacts& F = E->facts;
+  snprintf(E->last_kernel, sizeof E->last_kernel, "%s", c.name);
+  if (c.family != Family::z64) return -1;
+  return launch_z64(p, c, z64_tiles(F.max_m), z64_tiles(F.max_n), 8 * F.order_len) ? 0 : -1;
+}
+
+// The numeric phase for every element type; the scalars are (re, im) pairs whose imaginary parts are zero for real data.
+static int numeric_phase(void* handle, libsmm_acc_data_t datatype, const double alpha[2], const dbcsr_amd_bcsr* a, const dbcsr_amd_bcsr* b,
+                         const double beta[2], const dbcsr_amd_bcsr* c_in, dbcsr_amd_bcsr* c_out, void* stream);
+
 }  // namespace dbcsr_amd
 
 using namespace dbcsr_amd;
@@ -312,7 +327,7 @@ int dbcsr_amd_mm_symbolic_filtered(void* handle, libsmm_acc_data_t datatype, dou
   if (!E || !a || !b || !c_in || !c_out_row_p || !counts) return -1;
   E->drop_pending = 0.0;   // (an announced final filter belongs to ONE numeric phase: a new symbolic phase cancels whatever an abandoned multiply left)
   const bool filtering = filter_eps > 0.0;
-  if (filtering && datatype != dbcsr_type_real_8 && datatype != dbcsr_type_real_4) return -10;
+  if (filtering && datatype != dbcsr_type_real_8 && datatype != dbcsr_type_real_4 && datatype != dbcsr_type_complex_8) return -10;
   if (a->nblkcols != b->nblkrows || a->nblkrows != c_in->nblkrows || b->nblkcols != c_in->nblkcols) {
     fprintf(stderr, "dbcsr_amd_mm_symbolic: incompatible block dimensions\n");
     return -2;
@@ -388,6 +403,11 @@ int dbcsr_amd_mm_symbolic_filtered(void* handle, libsmm_acc_data_t datatype, dou
                          static_cast<const double*>(a->data), a->row_blk_size, a->col_blk_size, nbr, sa, 1.0, E->a_norms.p, (double*)nullptr);
       hipLaunchKernelGGL((bcsr_block_norms<double>), grid_for((int64_t)nbk * sb * 64), dim3(256), 0, st, b->row_p, b->col_i, b->blk_p,
                          static_cast<const double*>(b->data), b->row_blk_size, b->col_blk_size, nbk, sb, alpha, E->b_norms.p, (double*)nullptr);
+    } else if (datatype == dbcsr_type_complex_8) {   // (alpha is |alpha| here: the rule uses ||alpha * B||)
+      hipLaunchKernelGGL((bcsr_block_norms<z64>), grid_for((int64_t)nbr * sa * 64), dim3(256), 0, st, a->row_p, a->col_i, a->blk_p,
+                         static_cast<const z64*>(a->data), a->row_blk_size, a->col_blk_size, nbr, sa, 1.0, E->a_norms.p, (double*)nullptr);
+      hipLaunchKernelGGL((bcsr_block_norms<z64>), grid_for((int64_t)nbk * sb * 64), dim3(256), 0, st, b->row_p, b->col_i, b->blk_p,
+                         static_cast<const z64*>(b->data), b->row_blk_size, b->col_blk_size, nbk, sb, alpha, E->b_norms.p, (double*)nullptr);
     } else {
       hipLaunchKernelGGL((bcsr_block_norms<float>), grid_for((int64_t)nbr * sa * 64), dim3(256), 0, st, a->row_p, a->col_i, a->blk_p,
                          static_cast<const float*>(a->data), a->row_blk_size, a->col_blk_size, nbr, sa, 1.0, E->a_norms.p, (double*)nullptr);
@@ -565,12 +585,31 @@ int dbcsr_amd_mm_symbolic_filtered(void* handle, libsmm_acc_data_t datatype, dou
 
 int dbcsr_amd_mm_numeric(void* handle, libsmm_acc_data_t datatype, double alpha, const dbcsr_amd_bcsr* a, const dbcsr_amd_bcsr* b,
                          double beta, const dbcsr_amd_bcsr* c_in, dbcsr_amd_bcsr* c_out, void* stream) {
+  const double al[2] = {alpha, 0.0}, be[2] = {beta, 0.0};   // (complex_8: the scalars mean x + 0i)
+  return numeric_phase(handle, datatype, al, a, b, be, c_in, c_out, stream);
+}
+
+int dbcsr_amd_mm_numeric_z(void* handle, const double alpha[2], const dbcsr_amd_bcsr* a, const dbcsr_amd_bcsr* b, const double beta[2],
+                           const dbcsr_amd_bcsr* c_in, dbcsr_amd_bcsr* c_out, void* stream) {
+  if (!alpha || !beta) return -1;
+  return numeric_phase(handle, dbcsr_type_complex_8, alpha, a, b, beta, c_in, c_out, stream);
+}
+
+#include "mm_engine_ops.h"   // init_c, crop, filter, checksum, fill, transpose, twin moves, statistics
+
+}  // extern "C"
+
+namespace dbcsr_amd {
+
+static int numeric_phase(void* handle, libsmm_acc_data_t datatype, const double alpha_z[2], const dbcsr_amd_bcsr* a, const dbcsr_amd_bcsr* b,
+                         const double beta_z[2], const dbcsr_amd_bcsr* c_in, dbcsr_amd_bcsr* c_out, void* stream) {
+  const double alpha = alpha_z[0], beta = beta_z[0];
   Engine* E = static_cast<Engine*>(handle);
   if (!E || !E->valid || !a || !b || !c_in || !c_out) {
     fprintf(stderr, "dbcsr_amd_mm_numeric: no valid symbolic phase for this handle\n");
     return -1;
   }
-  if (datatype != dbcsr_type_real_8 && datatype != dbcsr_type_real_4) return -10;
+  if (datatype != dbcsr_type_real_8 && datatype != dbcsr_type_real_4 && datatype != dbcsr_type_complex_8) return -10;
   hipStream_t st = stream_of(stream);
   SizeFacts& F = E->facts;
   const int64_t nblk = F.c_nblks;
@@ -589,9 +628,10 @@ int dbcsr_amd_mm_numeric(void* handle, libsmm_acc_data_t datatype, double alpha,
   // 2. the choice (mm_choose.h), from the symbolic phase's facts and those of this call
   F.nbc = b->nblkcols;
   F.fp64 = datatype == dbcsr_type_real_8;
+  F.cplx = datatype == dbcsr_type_complex_8;
   F.filter_active = E->filter.a_norms != nullptr;
   // in-place accumulation (Cannon ticks after the first): C blocks without products in this call are left untouched
-  F.skip_empty = (c_out->data == c_in->data && F.retain && beta == 1.0) ? 1 : 0;
+  F.skip_empty = (c_out->data == c_in->data && F.retain && beta == 1.0 && beta_z[1] == 0.0) ? 1 : 0;
   const NumericChoice ch = choose_numeric(F, E->sw, E->lab);
   // 3. what the choice wants set up: launch-order work records (descriptor + first product in one read) ...
   const Work* work = nullptr;
@@ -622,8 +662,9 @@ int dbcsr_amd_mm_numeric(void* handle, libsmm_acc_data_t datatype, double alpha,
   }
   ACC_CHECK(hipEventRecord(E->ev[1], st));
   // 4. the launch
-  if ((F.fp64 ? launch_f64(E, ch, numeric_args<double>(E, st, a, b, c_in, c_out, alpha, beta, work, norms, reuse), E->lab)
-              : launch_f32(E, ch, numeric_args<float>(E, st, a, b, c_in, c_out, alpha, beta, work, norms, reuse))) != 0) {
+  if ((F.cplx ? launch_z64_family(E, ch, numeric_args<z64>(E, st, a, b, c_in, c_out, z64(alpha, alpha_z[1]), z64(beta, beta_z[1]), work, norms, reuse))
+       : F.fp64 ? launch_f64(E, ch, numeric_args<double>(E, st, a, b, c_in, c_out, alpha, beta, work, norms, reuse), E->lab)
+                : launch_f32(E, ch, numeric_args<float>(E, st, a, b, c_in, c_out, (float)alpha, (float)beta, work, norms, reuse))) != 0) {
     fprintf(stderr, "dbcsr_amd_mm_numeric: launching %s failed\n", E->last_kernel);
     return -1;
   }
@@ -640,6 +681,4 @@ int dbcsr_amd_mm_numeric(void* handle, libsmm_acc_data_t datatype, double alpha,
   return check(hipGetLastError(), "dbcsr_amd_mm_numeric", __FILE__, __LINE__);
 }
 
-#include "mm_engine_ops.h"   // init_c, crop, filter, checksum, fill, transpose, twin moves, statistics
-
-}  // extern "C"
+}  // namespace dbcsr_amd

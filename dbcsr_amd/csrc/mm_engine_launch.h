@@ -182,4 +182,23 @@ static void launch_small_f64(const NumericArgs<double>& p, const NumericChoice& 
                      p.work, c.group, npos);
 }
 
+// complex_8: one wave per C block (launch position), c.ww waves per workgroup, the instance of the multiply's largest block (mm_numeric_z64.h)
+static bool launch_z64(const NumericArgs<z64>& p, const NumericChoice& c, int ma, int nc, int64_t npos) {
+  if (!z64_has(ma, nc) || c.grid == 0) return false;
+  const int* order = npos > 0 ? p.order : nullptr;
+  switch (ma * 8 + nc) {
+#define DBCSR_Z64_CASE(A_, B_)                                                                                                                  \
+  case A_ * 8 + B_:                                                                                                                             \
+    hipLaunchKernelGGL((mm_numeric_z64<A_, B_>), dim3(c.grid), dim3(64 * c.ww), c.lds_bytes, p.st, p.descs, p.nblk, p.entries, p.a, p.b,        \
+                       p.c_out, p.c_in, p.alpha.re, p.alpha.im, p.beta.re, p.beta.im, c.flags, order, npos);                                    \
+    return true;
+    DBCSR_Z64_CASE(1, 1) DBCSR_Z64_CASE(1, 2) DBCSR_Z64_CASE(1, 3) DBCSR_Z64_CASE(1, 4)
+    DBCSR_Z64_CASE(2, 1) DBCSR_Z64_CASE(2, 2) DBCSR_Z64_CASE(2, 3) DBCSR_Z64_CASE(2, 4)
+    DBCSR_Z64_CASE(3, 1) DBCSR_Z64_CASE(3, 2) DBCSR_Z64_CASE(3, 3) DBCSR_Z64_CASE(3, 4)
+    DBCSR_Z64_CASE(4, 1) DBCSR_Z64_CASE(4, 2) DBCSR_Z64_CASE(4, 3) DBCSR_Z64_CASE(4, 4)
+#undef DBCSR_Z64_CASE
+    default: return false;
+  }
+}
+
 #endif

@@ -4,15 +4,15 @@
 #ifndef DBCSR_AMD_MM_ENGINE_OPS_H
 #define DBCSR_AMD_MM_ENGINE_OPS_H
 
-int dbcsr_amd_mm_init_c(void* handle, libsmm_acc_data_t datatype, double beta, const dbcsr_amd_bcsr* c_in, dbcsr_amd_bcsr* c_out,
-                        void* stream) {
+static int init_c_any(void* handle, libsmm_acc_data_t datatype, double beta, double beta_im, const dbcsr_amd_bcsr* c_in, dbcsr_amd_bcsr* c_out,
+                      void* stream) {
   Engine* E = static_cast<Engine*>(handle);
   if (E) E->plan_numeric = false;  // the descriptors are rewritten below: a numeric phase that follows fills its lists again (the plan itself stands)
   if (!E || !E->valid || !c_in || !c_out) {
     fprintf(stderr, "dbcsr_amd_mm_init_c: no valid symbolic phase for this handle\n");
     return -1;
   }
-  if (datatype != dbcsr_type_real_8 && datatype != dbcsr_type_real_4) return -10;
+  if (datatype != dbcsr_type_real_8 && datatype != dbcsr_type_real_4 && datatype != dbcsr_type_complex_8) return -10;
   hipStream_t st = stream_of(stream);
   const int nbr = E->facts.nbr, W = E->W;
   const int64_t nblk = E->facts.c_nblks;
@@ -26,10 +26,23 @@ int dbcsr_amd_mm_init_c(void* handle, libsmm_acc_data_t datatype, double beta, c
   if (datatype == dbcsr_type_real_8)
     hipLaunchKernelGGL((init_c_blocks<double>), grid_for(nblk * 64), dim3(256), 0, st, E->descs.p, nblk,
                        static_cast<double*>(c_out->data), static_cast<const double*>(c_in->data), beta);
+  else if (datatype == dbcsr_type_complex_8)
+    hipLaunchKernelGGL((init_c_blocks<z64>), grid_for(nblk * 64), dim3(256), 0, st, E->descs.p, nblk,
+                       static_cast<z64*>(c_out->data), static_cast<const z64*>(c_in->data), z64(beta, beta_im));
   else
     hipLaunchKernelGGL((init_c_blocks<float>), grid_for(nblk * 64), dim3(256), 0, st, E->descs.p, nblk,
                        static_cast<float*>(c_out->data), static_cast<const float*>(c_in->data), (float)beta);
   return check(hipGetLastError(), "dbcsr_amd_mm_init_c", __FILE__, __LINE__);
+}
+
+int dbcsr_amd_mm_init_c(void* handle, libsmm_acc_data_t datatype, double beta, const dbcsr_amd_bcsr* c_in, dbcsr_amd_bcsr* c_out,
+                        void* stream) {
+  return init_c_any(handle, datatype, beta, 0.0, c_in, c_out, stream);   // (complex_8: beta + 0i)
+}
+
+int dbcsr_amd_mm_init_c_z(void* handle, const double beta[2], const dbcsr_amd_bcsr* c_in, dbcsr_amd_bcsr* c_out, void* stream) {
+  if (!beta) return -1;
+  return init_c_any(handle, dbcsr_type_complex_8, beta[0], beta[1], c_in, c_out, stream);
 }
 
 
@@ -54,7 +67,7 @@ int dbcsr_amd_bcsr_crop_count(void* handle, libsmm_acc_data_t datatype, const db
   Engine* E = static_cast<Engine*>(handle);
   if (E) plan_invalidate(E);  // this call uses (or changes what feeds) the engine's work areas: the next multiply runs its own symbolic phase
   if (!E || !m || !new_row_p || !new_nblks || !new_nze) return -1;
-  if (datatype != dbcsr_type_real_8 && datatype != dbcsr_type_real_4) return -10;
+  if (datatype != dbcsr_type_real_8 && datatype != dbcsr_type_real_4 && datatype != dbcsr_type_complex_8) return -10;
   hipStream_t st = stream_of(stream);
   const int nbr = m->nblkrows;
   const int64_t nb = m->nblks;
@@ -101,13 +114,17 @@ int dbcsr_amd_bcsr_crop_apply(void* handle, libsmm_acc_data_t datatype, const db
     hipLaunchKernelGGL((crop_compact<float>), grid_for((int64_t)nbr * 64), dim3(256), 0, st, src->row_p, src->col_i, src->blk_p,
                        static_cast<const float*>(src->data), src->row_blk_size, src->col_blk_size, E->off_a.p, E->off_b.p, nbr,
                        E->crop_win, E->keep.p, E->prod_start.p, E->c_blk_p_ws.p, dst->col_i, dst->blk_p, static_cast<float*>(dst->data));
+  else if (datatype == dbcsr_type_complex_8)
+    hipLaunchKernelGGL((crop_compact<z64>), grid_for((int64_t)nbr * 64), dim3(256), 0, st, src->row_p, src->col_i, src->blk_p,
+                       static_cast<const z64*>(src->data), src->row_blk_size, src->col_blk_size, E->off_a.p, E->off_b.p, nbr,
+                       E->crop_win, E->keep.p, E->prod_start.p, E->c_blk_p_ws.p, dst->col_i, dst->blk_p, static_cast<z64*>(dst->data));
   else
     return -10;
   return check(hipGetLastError(), "dbcsr_amd_bcsr_crop_apply", __FILE__, __LINE__);
 }
 
-int dbcsr_amd_bcsr_scale_window(void* handle, libsmm_acc_data_t datatype, dbcsr_amd_bcsr* m, double beta, int64_t row_lo, int64_t row_hi,
-                                int64_t col_lo, int64_t col_hi, void* stream) {
+static int scale_window_any(void* handle, libsmm_acc_data_t datatype, dbcsr_amd_bcsr* m, double beta, double beta_im, int64_t row_lo, int64_t row_hi,
+                            int64_t col_lo, int64_t col_hi, void* stream) {
   Engine* E = static_cast<Engine*>(handle);
   if (!E || !m) return -1;
   hipStream_t st = stream_of(stream);
@@ -122,9 +139,23 @@ int dbcsr_amd_bcsr_scale_window(void* handle, libsmm_acc_data_t datatype, dbcsr_
   else if (datatype == dbcsr_type_real_4)
     hipLaunchKernelGGL((scale_window<float>), grid_for((int64_t)nbr * 64), dim3(256), 0, st, m->row_p, m->col_i, m->blk_p,
                        static_cast<float*>(m->data), m->row_blk_size, m->col_blk_size, E->off_a.p, E->off_b.p, nbr, w, (float)beta);
+  else if (datatype == dbcsr_type_complex_8)
+    hipLaunchKernelGGL((scale_window<z64>), grid_for((int64_t)nbr * 64), dim3(256), 0, st, m->row_p, m->col_i, m->blk_p,
+                       static_cast<z64*>(m->data), m->row_blk_size, m->col_blk_size, E->off_a.p, E->off_b.p, nbr, w, z64(beta, beta_im));
   else
     return -10;
   return check(hipGetLastError(), "dbcsr_amd_bcsr_scale_window", __FILE__, __LINE__);
+}
+
+int dbcsr_amd_bcsr_scale_window(void* handle, libsmm_acc_data_t datatype, dbcsr_amd_bcsr* m, double beta, int64_t row_lo, int64_t row_hi,
+                                int64_t col_lo, int64_t col_hi, void* stream) {
+  return scale_window_any(handle, datatype, m, beta, 0.0, row_lo, row_hi, col_lo, col_hi, stream);   // (complex_8: beta + 0i)
+}
+
+int dbcsr_amd_bcsr_scale_window_z(void* handle, dbcsr_amd_bcsr* m, const double beta[2], int64_t row_lo, int64_t row_hi, int64_t col_lo,
+                                  int64_t col_hi, void* stream) {
+  if (!beta) return -1;
+  return scale_window_any(handle, dbcsr_type_complex_8, m, beta[0], beta[1], row_lo, row_hi, col_lo, col_hi, stream);
 }
 
 int dbcsr_amd_bcsr_filter_count(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, double eps, int32_t* new_row_p,
@@ -132,7 +163,7 @@ int dbcsr_amd_bcsr_filter_count(void* handle, libsmm_acc_data_t datatype, const 
   Engine* E = static_cast<Engine*>(handle);
   if (E) plan_invalidate(E);  // this call uses (or changes what feeds) the engine's work areas: the next multiply runs its own symbolic phase
   if (!E || !m || !new_row_p || !new_nblks || !new_nze) return -1;
-  if (datatype != dbcsr_type_real_8 && datatype != dbcsr_type_real_4) return -10;
+  if (datatype != dbcsr_type_real_8 && datatype != dbcsr_type_real_4 && datatype != dbcsr_type_complex_8) return -10;
   hipStream_t st = stream_of(stream);
   const int nbr = m->nblkrows;
   const int64_t nb = m->nblks;
@@ -160,6 +191,9 @@ int dbcsr_amd_bcsr_filter_count(void* handle, libsmm_acc_data_t datatype, const 
     } else if (datatype == dbcsr_type_real_8)
       hipLaunchKernelGGL((bcsr_block_norms<double>), grid_for((int64_t)nbr * sm * 64), dim3(256), 0, st, m->row_p, m->col_i, m->blk_p,
                          static_cast<const double*>(m->data), m->row_blk_size, m->col_blk_size, nbr, sm, 1.0, (float*)nullptr, E->norms64.p);
+    else if (datatype == dbcsr_type_complex_8)   // block norm^2 = sum re^2 + im^2
+      hipLaunchKernelGGL((bcsr_block_norms<z64>), grid_for((int64_t)nbr * sm * 64), dim3(256), 0, st, m->row_p, m->col_i, m->blk_p,
+                         static_cast<const z64*>(m->data), m->row_blk_size, m->col_blk_size, nbr, sm, 1.0, (float*)nullptr, E->norms64.p);
     else
       hipLaunchKernelGGL((bcsr_block_norms<float>), grid_for((int64_t)nbr * sm * 64), dim3(256), 0, st, m->row_p, m->col_i, m->blk_p,
                          static_cast<const float*>(m->data), m->row_blk_size, m->col_blk_size, nbr, sm, 1.0, (float*)nullptr, E->norms64.p);
@@ -193,6 +227,10 @@ int dbcsr_amd_bcsr_filter_apply(void* handle, libsmm_acc_data_t datatype, const 
     hipLaunchKernelGGL((filter_compact<float>), grid_for((int64_t)nbr * sc * 64), dim3(256), 0, st, src->row_p, src->col_i, src->blk_p,
                        static_cast<const float*>(src->data), src->row_blk_size, src->col_blk_size, nbr, sc, E->keep.p, E->prod_start.p,
                        E->c_blk_p_ws.p, dst->col_i, dst->blk_p, static_cast<float*>(dst->data));
+  else if (datatype == dbcsr_type_complex_8)
+    hipLaunchKernelGGL((filter_compact<z64>), grid_for((int64_t)nbr * sc * 64), dim3(256), 0, st, src->row_p, src->col_i, src->blk_p,
+                       static_cast<const z64*>(src->data), src->row_blk_size, src->col_blk_size, nbr, sc, E->keep.p, E->prod_start.p,
+                       E->c_blk_p_ws.p, dst->col_i, dst->blk_p, static_cast<z64*>(dst->data));
   else
     return -10;
   return check(hipGetLastError(), "dbcsr_amd_bcsr_filter_apply", __FILE__, __LINE__);
@@ -220,6 +258,7 @@ int dbcsr_amd_mm_set_filter_in_place(void* handle, int on) {
 int dbcsr_amd_bcsr_checksum(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, double* out2, void* stream) {
   Engine* E = static_cast<Engine*>(handle);
   if (!E || !m || !out2) return -1;
+  if (datatype != dbcsr_type_real_8 && datatype != dbcsr_type_real_4) return -10;   // (complex data: not offered, see the header)
   hipStream_t st = stream_of(stream);
   const int nbr = m->nblkrows;
   out2[0] = out2[1] = 0.0;
@@ -256,7 +295,11 @@ int dbcsr_amd_bcsr_fill_random_dist(void* handle, libsmm_acc_data_t datatype, co
   if (datatype == dbcsr_type_real_8)
     hipLaunchKernelGGL(fill_random_f64, grid_for((int64_t)m->nblkrows * 64), dim3(256), 0, st, m->row_p, m->col_i, m->blk_p,
                        static_cast<double*>(m->data), m->row_blk_size, m->col_blk_size, m->nblkrows, m->nblkcols, counter, row_gid, col_gid,
-                       nblkrows_global);
+                       nblkrows_global, 1);
+  else if (datatype == dbcsr_type_complex_8)   // zlarnv(idist = 1): the dlarnv stream of the block's seed, (re, im) pairs
+    hipLaunchKernelGGL(fill_random_f64, grid_for((int64_t)m->nblkrows * 64), dim3(256), 0, st, m->row_p, m->col_i, m->blk_p,
+                       static_cast<double*>(m->data), m->row_blk_size, m->col_blk_size, m->nblkrows, m->nblkcols, counter, row_gid, col_gid,
+                       nblkrows_global, 2);
   else if (datatype == dbcsr_type_real_4)
     hipLaunchKernelGGL(fill_random_f32, grid_for(m->nblks), dim3(256), 0, st, m->row_p, m->col_i, m->blk_p,
                        static_cast<float*>(m->data), m->row_blk_size, m->col_blk_size, m->nblkrows, m->nblkcols, counter, row_gid, col_gid,
@@ -266,11 +309,11 @@ int dbcsr_amd_bcsr_fill_random_dist(void* handle, libsmm_acc_data_t datatype, co
   return check(hipGetLastError(), "dbcsr_amd_bcsr_fill_random", __FILE__, __LINE__);
 }
 
-int dbcsr_amd_bcsr_transpose(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, dbcsr_amd_bcsr* dst, void* stream) {
+static int transpose_any(void* handle, libsmm_acc_data_t datatype, bool conj, const dbcsr_amd_bcsr* src, dbcsr_amd_bcsr* dst, void* stream) {
   Engine* E = static_cast<Engine*>(handle);
   if (E) plan_invalidate(E);  // this call uses (or changes what feeds) the engine's work areas: the next multiply runs its own symbolic phase
   if (!E || !src || !dst) return -1;
-  if (datatype != dbcsr_type_real_8 && datatype != dbcsr_type_real_4) return -10;
+  if (datatype != dbcsr_type_real_8 && datatype != dbcsr_type_real_4 && datatype != dbcsr_type_complex_8) return -10;
   hipStream_t st = stream_of(stream);
   const int s_nbr = src->nblkrows, t_nbr = src->nblkcols;
   const int Wt = (s_nbr + 31) / 32;
@@ -291,6 +334,14 @@ int dbcsr_amd_bcsr_transpose(void* handle, libsmm_acc_data_t datatype, const dbc
       hipLaunchKernelGGL((transpose_fill<double>), grid_for((int64_t)s_nbr * 64), dim3(256), 0, st, src->row_p, src->col_i, src->blk_p,
                          static_cast<const double*>(src->data), src->row_blk_size, src->col_blk_size, E->c_bm.p, E->c_pre.p, dst->row_p,
                          E->c_blk_p_ws.p, s_nbr, Wt, dst->col_i, dst->blk_p, static_cast<double*>(dst->data));
+    else if (datatype == dbcsr_type_complex_8 && conj)
+      hipLaunchKernelGGL((transpose_fill<z64, true>), grid_for((int64_t)s_nbr * 64), dim3(256), 0, st, src->row_p, src->col_i, src->blk_p,
+                         static_cast<const z64*>(src->data), src->row_blk_size, src->col_blk_size, E->c_bm.p, E->c_pre.p, dst->row_p,
+                         E->c_blk_p_ws.p, s_nbr, Wt, dst->col_i, dst->blk_p, static_cast<z64*>(dst->data));
+    else if (datatype == dbcsr_type_complex_8)
+      hipLaunchKernelGGL((transpose_fill<z64>), grid_for((int64_t)s_nbr * 64), dim3(256), 0, st, src->row_p, src->col_i, src->blk_p,
+                         static_cast<const z64*>(src->data), src->row_blk_size, src->col_blk_size, E->c_bm.p, E->c_pre.p, dst->row_p,
+                         E->c_blk_p_ws.p, s_nbr, Wt, dst->col_i, dst->blk_p, static_cast<z64*>(dst->data));
     else
       hipLaunchKernelGGL((transpose_fill<float>), grid_for((int64_t)s_nbr * 64), dim3(256), 0, st, src->row_p, src->col_i, src->blk_p,
                          static_cast<const float*>(src->data), src->row_blk_size, src->col_blk_size, E->c_bm.p, E->c_pre.p, dst->row_p,
@@ -298,6 +349,14 @@ int dbcsr_amd_bcsr_transpose(void* handle, libsmm_acc_data_t datatype, const dbc
   }
   dst->nblks = src->nblks;
   return check(hipGetLastError(), "dbcsr_amd_bcsr_transpose", __FILE__, __LINE__);
+}
+
+int dbcsr_amd_bcsr_transpose(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, dbcsr_amd_bcsr* dst, void* stream) {
+  return transpose_any(handle, datatype, false, src, dst, stream);
+}
+
+int dbcsr_amd_bcsr_transpose_conj(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, dbcsr_amd_bcsr* dst, void* stream) {
+  return transpose_any(handle, datatype, true, src, dst, stream);   // (real data: the plain transpose)
 }
 
 int dbcsr_amd_bcsr_desymmetrize_count(void* handle, const dbcsr_amd_bcsr* src, int32_t* dst_row_p, int64_t* nblks, int64_t* nze, void* stream) {
@@ -407,7 +466,7 @@ int dbcsr_amd_mm_stats(void* handle, dbcsr_amd_mnk_stat* out, int max_entries, i
 }
 
 const char* dbcsr_amd_mm_kernel_name(libsmm_acc_data_t datatype) {
-  return datatype == dbcsr_type_real_4 ? "mm_numeric_f32" : "mm_numeric_f64";
+  return datatype == dbcsr_type_complex_8 ? "mm_numeric_z64" : datatype == dbcsr_type_real_4 ? "mm_numeric_f32" : "mm_numeric_f64";
 }
 
 const char* dbcsr_amd_mm_last_kernel(void* handle) {

@@ -199,10 +199,7 @@ __global__ void __launch_bounds__(256) bcsr_block_norms(const int* __restrict__ 
     const int ne = m * cs[col_i[b]];
     const T* d = data + blk_p[b];
     double s = 0.0;
-    for (int e = lane; e < ne; e += 64) {
-      const double x = scale * (double)d[e];
-      s += x * x;
-    }
+    for (int e = lane; e < ne; e += 64) s += scaled_norm2(scale, d[e]);   // (mm_complex.h; real data: (scale * x)^2)
     s = wave_sum(s);
     if (lane == 0) {
       if (norms) norms[b] = (float)s;

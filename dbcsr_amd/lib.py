@@ -36,6 +36,8 @@ MM_SYMBOLS = [
     "dbcsr_amd_bcsr_twin_count", "dbcsr_amd_bcsr_twin_apply", "dbcsr_amd_mm_set_canonical_product", "dbcsr_amd_multiply_symmetric_c",
     "dbcsr_amd_bcsr_desymmetrized", "dbcsr_amd_smm_last_kernel", "dbcsr_amd_multiply_symmetric_c_klimits",
     "dbcsr_amd_bcsr_filter_apply_index", "dbcsr_amd_mm_set_filter_in_place",
+    # complex_8: complex scalars as double[2] = {re, im}
+    "dbcsr_amd_mm_numeric_z", "dbcsr_amd_mm_init_c_z", "dbcsr_amd_bcsr_scale_window_z", "dbcsr_amd_bcsr_transpose_conj", "dbcsr_amd_multiply_z",
 ]
 
 
@@ -171,6 +173,12 @@ def load_library(lab=False):
     L.dbcsr_amd_mm_trust_plan.argtypes = [vp, C.c_int]
     L.dbcsr_amd_mm_expect_filter.argtypes = [vp, C.c_double]
     L.dbcsr_amd_mm_expect_filter.restype = C.c_int
+    Z = C.POINTER(C.c_double)   # a complex scalar: double[2] = {re, im}
+    L.dbcsr_amd_mm_numeric_z.argtypes = [vp, Z, BP, BP, Z, BP, BP, vp]
+    L.dbcsr_amd_mm_init_c_z.argtypes = [vp, Z, BP, BP, vp]
+    L.dbcsr_amd_bcsr_scale_window_z.argtypes = [vp, BP, Z, i64, i64, i64, i64, vp]
+    L.dbcsr_amd_bcsr_transpose_conj.argtypes = [vp, i32, BP, BP, vp]
+    L.dbcsr_amd_multiply_z.argtypes = [vp, C.c_char, C.c_char, Z, BP, BP, Z, BP, C.POINTER(i64), i32, C.c_double, BP, C.POINTER(i64), vp]
     if lab:   # diagnostics of the experimental dataflows (dbcsr_amd/csrc/mm_lab_api.h): the shipping build does not export them
         L.dbcsr_amd_mm_tile_stats.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
         L.dbcsr_amd_mm_band_stats.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]

@@ -17,7 +17,9 @@ def _dtype_code(dt):
         return _lib.dbcsr_type_real_8
     if dt == torch.float32:
         return _lib.dbcsr_type_real_4
-    raise TypeError("dbcsr_amd supports real_8 and real_4 data, got %r" % (dt,))
+    if dt == torch.complex128:
+        return _lib.dbcsr_type_complex_8
+    raise TypeError("dbcsr_amd supports real_8 (float64), real_4 (float32) and complex_8 (complex128) data, got %r" % (dt,))
 
 
 class StreamHandle:

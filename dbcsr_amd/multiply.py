@@ -20,6 +20,12 @@ dbcsr_transpose = "T"
 dbcsr_conjugate_transpose = "C"
 
 
+def _z(x):
+    """a complex scalar as the C-ABI takes it: double[2] = {re, im}"""
+    x = complex(x)
+    return (C.c_double * 2)(x.real, x.imag)
+
+
 class MultiplyEngine:
     """Owns the native workspace (bitmaps, product lists) across calls."""
 
@@ -47,13 +53,17 @@ class MultiplyEngine:
             pass
 
     # ------------------------------------------------------------------
-    def transposed(self, M, stream=None):
+    def transposed(self, M, stream=None, conjugate=False):
+        """M^T, or with conjugate=True M^H (complex data; for real data the same matrix)"""
         st = StreamHandle(stream)
         out = DbcsrMatrix(M.col_blk_size, M.row_blk_size, torch.empty(M.nblkcols + 1, dtype=torch.int32, device=M.data.device),
                           torch.empty_like(M.col_i), torch.empty_like(M.blk_p),
                           torch.empty(M.nze, dtype=M.dtype, device=M.data.device), M.name + "^T")   # (the transpose is written packed)
         src, dst = M.desc(), out.desc(out=True)
-        rc = self.L.dbcsr_amd_bcsr_transpose(self.h, M.dtype_code, C.byref(src), C.byref(dst), st.ptr)
+        if conjugate and M.dtype.is_complex:
+            rc = self.L.dbcsr_amd_bcsr_transpose_conj(self.h, M.dtype_code, C.byref(src), C.byref(dst), st.ptr)
+        else:
+            rc = self.L.dbcsr_amd_bcsr_transpose(self.h, M.dtype_code, C.byref(src), C.byref(dst), st.ptr)
         if rc != 0:
             raise RuntimeError("dbcsr_amd_bcsr_transpose failed (%d)" % rc)
         return out
@@ -183,8 +193,11 @@ class MultiplyEngine:
                           torch.empty(counts.c_nblks, dtype=torch.int64, device=dev),
                           torch.empty(counts.c_nze, dtype=dtype, device=dev), Cm.name)
         cin, cout = Cm.desc(), out.desc(out=True)
-        rc = self.L.dbcsr_amd_mm_init_c(self.h, _lib.dbcsr_type_real_8 if dtype == torch.float64 else _lib.dbcsr_type_real_4,
-                                        float(beta), C.byref(cin), C.byref(cout), st.ptr)
+        if dtype.is_complex:
+            rc = self.L.dbcsr_amd_mm_init_c_z(self.h, _z(beta), C.byref(cin), C.byref(cout), st.ptr)
+        else:
+            rc = self.L.dbcsr_amd_mm_init_c(self.h, _lib.dbcsr_type_real_8 if dtype == torch.float64 else _lib.dbcsr_type_real_4,
+                                            float(beta), C.byref(cin), C.byref(cout), st.ptr)
         if rc != 0:
             raise RuntimeError("dbcsr_amd_mm_init_c failed (%d)" % rc)
         return out
@@ -202,8 +215,11 @@ class MultiplyEngine:
         if rc != 0:
             raise RuntimeError("dbcsr_amd_mm_symbolic failed (%d)" % rc)
         cout = _lib.BcsrDesc(c.nblkrows, c.nblkcols, c.row_blk_size, c.col_blk_size, row_p.data_ptr(), c.col_i, c.blk_p, c.data, c.nblks)
-        rc = self.L.dbcsr_amd_mm_numeric(self.h, Cacc.dtype_code, float(alpha), C.byref(a), C.byref(b), 1.0, C.byref(c), C.byref(cout),
-                                         st.ptr)
+        if Cacc.dtype.is_complex:
+            rc = self.L.dbcsr_amd_mm_numeric_z(self.h, _z(alpha), C.byref(a), C.byref(b), _z(1.0), C.byref(c), C.byref(cout), st.ptr)
+        else:
+            rc = self.L.dbcsr_amd_mm_numeric(self.h, Cacc.dtype_code, float(alpha), C.byref(a), C.byref(b), 1.0, C.byref(c), C.byref(cout),
+                                             st.ptr)
         if rc != 0:
             raise RuntimeError("dbcsr_amd_mm_numeric failed (%d)" % rc)
         return counts
@@ -221,8 +237,11 @@ class MultiplyEngine:
                           torch.empty(counts.c_nblks, dtype=torch.int64, device=dev),
                           out_data if out_data is not None else torch.empty(counts.c_nze, dtype=dtype, device=dev), Cm.name)
         a, b, cin, cout = A.desc(), B.desc(), Cm.desc(), out.desc(out=True)
-        rc = self.L.dbcsr_amd_mm_numeric(self.h, out.dtype_code, float(alpha), C.byref(a), C.byref(b), float(beta), C.byref(cin),
-                                         C.byref(cout), st.ptr)
+        if out.dtype.is_complex:
+            rc = self.L.dbcsr_amd_mm_numeric_z(self.h, _z(alpha), C.byref(a), C.byref(b), _z(beta), C.byref(cin), C.byref(cout), st.ptr)
+        else:
+            rc = self.L.dbcsr_amd_mm_numeric(self.h, out.dtype_code, float(alpha), C.byref(a), C.byref(b), float(beta), C.byref(cin),
+                                             C.byref(cout), st.ptr)
         if rc != 0:
             raise RuntimeError("dbcsr_amd_mm_numeric failed (%d)" % rc)
         return out
@@ -269,6 +288,8 @@ class MultiplyEngine:
         it builds the multiplication images, dbcsr_mm_cannon.F:284, 351-379)."""
         if M.symmetry == "N":
             return M
+        if M.dtype.is_complex:
+            raise NotImplementedError("complex matrices with symmetry %r (hermitian / antihermitian matrices are not offered yet)" % (M.symmetry,))
         if M.symmetry not in ("S", "A"):
             raise ValueError("unsupported matrix symmetry %r (real data: 'N', 'S', 'A')" % (M.symmetry,))
         st = StreamHandle(stream)
@@ -345,7 +366,10 @@ class MultiplyEngine:
         r0, r1 = (-1, -1) if row_bounds is None else (int(row_bounds[0]), int(row_bounds[1]))
         c0, c1 = (-1, -1) if col_bounds is None else (int(col_bounds[0]), int(col_bounds[1]))
         d = out.desc(out=True)
-        rc = self.L.dbcsr_amd_bcsr_scale_window(self.h, M.dtype_code, C.byref(d), float(beta), r0, r1, c0, c1, st.ptr)
+        if M.dtype.is_complex:
+            rc = self.L.dbcsr_amd_bcsr_scale_window_z(self.h, C.byref(d), _z(beta), r0, r1, c0, c1, st.ptr)
+        else:
+            rc = self.L.dbcsr_amd_bcsr_scale_window(self.h, M.dtype_code, C.byref(d), float(beta), r0, r1, c0, c1, st.ptr)
         if rc != 0:
             raise RuntimeError("dbcsr_amd_bcsr_scale_window failed (%d)" % rc)
         return out
@@ -365,6 +389,8 @@ class MultiplyEngine:
     KCHUNK_MIN_PRODUCTS = 48.0
 
     def _auto_kchunks(self, A, filter_eps, B=None):
+        if A.dtype.is_complex:   # complex multiplies run in one pass
+            return 1
         if filter_eps and filter_eps > 0:  # the on-the-fly filter counts the blocks of a whole A row (dbcsr_mm_cannon.F:1100-1110)
             return 1
         forced = os.environ.get("DBCSR_AMD_MM_KCHUNKS")
@@ -431,6 +457,9 @@ class MultiplyEngine:
     def multiply_local(self, alpha, A, B, beta, Cm, retain_sparsity=False, stream=None, filter_eps=0.0, kchunks=None):
         """C_out = beta*Cm + alpha*A*B for already-oriented operands; returns (C_out, counts)."""
         n = self._auto_kchunks(A, filter_eps, B) if kchunks is None else int(kchunks)
+        cplx = A.dtype.is_complex
+        if cplx:
+            n = 1   # (no k passes for complex data)
         if filter_eps and filter_eps > 0.0 and n > 1:
             raise ValueError("multiply_local: k passes cannot be combined with filter_eps (the on-the-fly filter counts the blocks of a whole A row)")
         if n > 1 and A.nblkcols >= n:
@@ -487,7 +516,8 @@ class MultiplyEngine:
         a, b, cin = A.desc(), B.desc(), Cm.desc()
         row_p = torch.empty(Cm.nblkrows + 1, dtype=torch.int32, device=dev)
         counts = _lib.MmCounts()
-        rc = self.L.dbcsr_amd_mm_symbolic_filtered(self.h, A.dtype_code, float(alpha), float(filter_eps or 0.0), C.byref(a), C.byref(b),
+        # (complex data: the on-the-fly filter's rule uses ||alpha * B||, so it is handed |alpha|)
+        rc = self.L.dbcsr_amd_mm_symbolic_filtered(self.h, A.dtype_code, abs(complex(alpha)) if cplx else float(alpha), float(filter_eps or 0.0), C.byref(a), C.byref(b),
                                                    C.byref(cin), 1 if retain_sparsity else 0, row_p.data_ptr(), C.byref(counts), st.ptr)
         if rc != 0:
             raise RuntimeError("dbcsr_amd_mm_symbolic failed (%d)" % rc)
@@ -498,8 +528,11 @@ class MultiplyEngine:
         if filter_eps and filter_eps > 0 and not retain_sparsity and os.environ.get("DBCSR_AMD_MM_EXPECT_FILTER", "1") != "0":
             # the product goes straight into the block filter below with the same eps (dbcsr_mm_multrec.F:373-383): blocks it will drop need not be written
             self.L.dbcsr_amd_mm_expect_filter(self.h, float(filter_eps))
-        rc = self.L.dbcsr_amd_mm_numeric(self.h, A.dtype_code, float(alpha), C.byref(a), C.byref(b), float(beta), C.byref(cin),
-                                         C.byref(cout), st.ptr)
+        if cplx:
+            rc = self.L.dbcsr_amd_mm_numeric_z(self.h, _z(alpha), C.byref(a), C.byref(b), _z(beta), C.byref(cin), C.byref(cout), st.ptr)
+        else:
+            rc = self.L.dbcsr_amd_mm_numeric(self.h, A.dtype_code, float(alpha), C.byref(a), C.byref(b), float(beta), C.byref(cin),
+                                             C.byref(cout), st.ptr)
         if rc != 0:
             raise RuntimeError("dbcsr_amd_mm_numeric failed (%d)" % rc)
         self.last_launch_flop, self.last_kchunks = counts.flop, 1
@@ -530,6 +563,11 @@ def dbcsr_multiply(transa, transb, alpha, matrix_a, matrix_b, beta, matrix_c, fi
         raise TypeError("dbcsr_multiply: data types of A, B and C differ")
     E = engine or default_engine()
     c_symm = getattr(matrix_c, "symmetry", "N")
+    cplx = matrix_c.dtype.is_complex
+    if cplx and any(getattr(m, "symmetry", "N") != "N" for m in (matrix_a, matrix_b, matrix_c)):
+        raise NotImplementedError("dbcsr_multiply: complex matrices with symmetry (hermitian / antihermitian matrices are not offered yet)")
+    if not cplx and (isinstance(alpha, complex) or isinstance(beta, complex)):
+        raise TypeError("dbcsr_multiply: complex scalars with real matrices")
     if c_symm != "N":
         # Product matrix with symmetry (src/mm/dbcsr_mm.F:711-719): its index goes into canonical (checkerboard) form, only the blocks
         # stored in that form are computed (dbcsr_mm_csr.F:280-292), the result goes back to the stored triangle (row <= column).
@@ -548,8 +586,8 @@ def dbcsr_multiply(transa, transb, alpha, matrix_a, matrix_b, beta, matrix_c, fi
         matrix_c.adopt(up)
         return counts
     matrix_a, matrix_b = E.desymmetrized(matrix_a), E.desymmetrized(matrix_b)
-    A = E.transposed(matrix_a) if transa != "N" else matrix_a
-    B = E.transposed(matrix_b) if transb != "N" else matrix_b
+    A = E.transposed(matrix_a, conjugate=transa == "C") if transa != "N" else matrix_a   # ('C' == 'T' for real data)
+    B = E.transposed(matrix_b, conjugate=transb == "C") if transb != "N" else matrix_b
     if A.nblkcols != B.nblkrows or A.nblkrows != matrix_c.nblkrows or B.nblkcols != matrix_c.nblkcols:
         raise ValueError("dbcsr_multiply: incompatible block dimensions")
     limits = (first_row, last_row, first_column, last_column, first_k, last_k)
@@ -573,7 +611,7 @@ def dbcsr_multiply(transa, transb, alpha, matrix_a, matrix_b, beta, matrix_c, fi
     limited = any((fr, lr, fc, lc, fk, lk))
     # Product data is retained when retain_sparsity, beta != 0, or a row / column window ends inside C (dbcsr_mm.F:695-704);
     # otherwise the reference empties C before the multiplication (:865-870): old blocks vanish, their values are never read.
-    keep_product_data = bool(retain_sparsity) or beta != 0.0 or window_keeps
+    keep_product_data = bool(retain_sparsity) or beta != 0.0 or window_keeps   # (complex beta: a complex comparison, both parts zero)
     matrix_in, beta_eff = matrix_c, beta
     if not keep_product_data:
         matrix_in, beta_eff = E.empty_like(matrix_c), 1.0

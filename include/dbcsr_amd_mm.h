@@ -19,6 +19,14 @@
  * row_p / col_i / blk_p + one data area), 0-based, 64-bit block offsets,
  * blocks column-major.  ALL POINTERS ARE DEVICE POINTERS.
  *
+ * Data types: dbcsr_type_real_8, dbcsr_type_real_4 and dbcsr_type_complex_8 (COMPLEX(real_8): (re, im) pairs of doubles,
+ * interleaved; an element offset in blk_p counts complex elements).  Every entry with a datatype argument takes complex_8 unless
+ * it says otherwise below; the entries whose scalars are real doubles read them as x + 0i for complex data, and the _z entries
+ * take complex scalars as const double[2] = {re, im}.  NOT offered for complex_8 (they return -10, as every entry does for
+ * dbcsr_type_complex_4): libsmm_acc_process / _transpose (the reference's accelerator path returns -10 for complex stacks too),
+ * matrices with symmetry (dbcsr_amd_bcsr_twin_*, _desymmetrize_*, _desymmetrized, dbcsr_amd_multiply_symmetric_c*: hermitian and
+ * antihermitian matrices are a follow-up), dbcsr_amd_bcsr_checksum, and dbcsr_amd_multiply (see dbcsr_amd_multiply_z).
+ *
  * Return: 0 ok, non-zero error (message on stderr).  Streams use the handle
  * convention of dbcsr_acc.h (pointer to hipStream_t, NULL = null stream).
  */
@@ -40,7 +48,7 @@ typedef struct dbcsr_amd_bcsr {
   int32_t* row_p;              /* [nblkrows+1] */
   int32_t* col_i;              /* [nblks], ascending inside a row */
   int64_t* blk_p;              /* [nblks], element offset of each block in data */
-  void* data;                  /* fp64 or fp32 elements */
+  void* data;                  /* fp64, fp32 or complex_8 (re, im) elements */
   int64_t nblks;
   uint64_t index_stamp;        /* generation of the index arrays above: 0 = unknown; a caller that owns them may set a value that it
                                   changes whenever it writes, frees or re-allocates one of them (see dbcsr_amd_mm_trust_plan).  Set to
@@ -76,14 +84,16 @@ int dbcsr_amd_mm_symbolic(void* handle, const dbcsr_amd_bcsr* a, const dbcsr_amd
 /* Symbolic product with on-the-fly filtering (dbcsr_mm_csr.F:276, dbcsr_mm_cannon.F:1040-1113): a product
  * A(i,k)*B(k,j) is skipped when ||A(i,k)||^2 * ||alpha*B(k,j)||^2 < (filter_eps / max(1, #blocks of A row i))^2
  * (single precision, as the reference); new C blocks are created only by surviving products.  Needs the data
- * areas of a and b (norms) and the alpha of the numeric call that follows.  filter_eps <= 0: same as above. */
+ * areas of a and b (norms) and the alpha of the numeric call that follows.  filter_eps <= 0: same as above.
+ * complex_8: block norm^2 = sum re^2 + im^2, and `alpha` is |alpha| of the numeric call (the rule uses ||alpha*B||). */
 int dbcsr_amd_mm_symbolic_filtered(void* handle, libsmm_acc_data_t datatype, double alpha, double filter_eps, const dbcsr_amd_bcsr* a,
   const dbcsr_amd_bcsr* b, const dbcsr_amd_bcsr* c_in, int retain_sparsity, int32_t* c_out_row_p, dbcsr_amd_mm_counts* counts,
   void* stream);
 
 /* Final block filter of a multiply (dbcsr_mm_multrec.F:694-748) / dbcsr_filter: blocks with sum x^2 < eps^2 are
  * dropped.  _count writes new_row_p [nblkrows+1] (device) and the new block/element counts (host, synchronises);
- * _apply then compacts index and data into caller-allocated dst arrays (dst->row_p = new_row_p). */
+ * _apply then compacts index and data into caller-allocated dst arrays (dst->row_p = new_row_p).
+ * complex_8: sum x^2 is sum re^2 + im^2. */
 int dbcsr_amd_bcsr_filter_count(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, double eps, int32_t* new_row_p,
   int64_t* new_nblks, int64_t* new_nze, void* stream);
 int dbcsr_amd_bcsr_filter_apply(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, dbcsr_amd_bcsr* dst, void* stream);
@@ -117,6 +127,9 @@ int dbcsr_amd_bcsr_crop_count(void* handle, libsmm_acc_data_t datatype, const db
 int dbcsr_amd_bcsr_crop_apply(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, dbcsr_amd_bcsr* dst, void* stream);
 int dbcsr_amd_bcsr_scale_window(void* handle, libsmm_acc_data_t datatype, dbcsr_amd_bcsr* m, double beta, int64_t row_lo,
   int64_t row_hi, int64_t col_lo, int64_t col_hi, void* stream);
+/* ... of a complex_8 matrix with a complex beta = {re, im} */
+int dbcsr_amd_bcsr_scale_window_z(void* handle, dbcsr_amd_bcsr* m, const double beta[2], int64_t row_lo, int64_t row_hi, int64_t col_lo,
+  int64_t col_hi, void* stream);
 
 /* Numeric phase.  c_out->row_p is the array written by the symbolic call;
  * col_i [c_nblks], blk_p [c_nblks] and data [c_nze] are allocated by the caller
@@ -125,9 +138,15 @@ int dbcsr_amd_bcsr_scale_window(void* handle, libsmm_acc_data_t datatype, dbcsr_
  * packed in index order (blk_p = running sum of the block sizes) -- which is how every matrix produced by this
  * library is laid out; a C_in with another placement must not be aliased (c_out->blk_p is rewritten to the packed
  * offsets).
- * datatype: dbcsr_type_real_8 or dbcsr_type_real_4.  Asynchronous on stream. */
+ * datatype: dbcsr_type_real_8, dbcsr_type_real_4 or dbcsr_type_complex_8 (alpha + 0i, beta + 0i).  Asynchronous on stream. */
 int dbcsr_amd_mm_numeric(void* handle, libsmm_acc_data_t datatype, double alpha, const dbcsr_amd_bcsr* a, const dbcsr_amd_bcsr* b,
   double beta, const dbcsr_amd_bcsr* c_in, dbcsr_amd_bcsr* c_out, void* stream);
+/* The numeric phase of a complex_8 multiply with complex scalars {re, im}: C_out = beta*C_in + alpha*A*B in complex arithmetic (kernel
+ * family mm_numeric_z64<MA,NC>: every block is written, an announced final filter -- dbcsr_amd_mm_expect_filter -- is ignored).
+ * In-place accumulation (c_out aliasing c_in after a retain_sparsity symbolic phase) leaves blocks without products untouched when
+ * beta == 1 + 0i. */
+int dbcsr_amd_mm_numeric_z(void* handle, const double alpha[2], const dbcsr_amd_bcsr* a, const dbcsr_amd_bcsr* b, const double beta[2],
+  const dbcsr_amd_bcsr* c_in, dbcsr_amd_bcsr* c_out, void* stream);
 
 /* Structure-only companion of the symbolic call, for multiplies whose products arrive in
  * several passes (the Cannon ticks of dbcsr_mm_cannon.F:1347-1704): emits C_out's index
@@ -137,22 +156,27 @@ int dbcsr_amd_mm_numeric(void* handle, libsmm_acc_data_t datatype, double alpha,
  * not touched. */
 int dbcsr_amd_mm_init_c(void* handle, libsmm_acc_data_t datatype, double beta, const dbcsr_amd_bcsr* c_in, dbcsr_amd_bcsr* c_out,
   void* stream);
+/* ... of a complex_8 product with a complex beta = {re, im} */
+int dbcsr_amd_mm_init_c_z(void* handle, const double beta[2], const dbcsr_amd_bcsr* c_in, dbcsr_amd_bcsr* c_out, void* stream);
 
 /* Transposed copy of a BCSR matrix on the device (dbcsr_new_transposed,
  * src/ops/dbcsr_transformations.F): dst index arrays/data are caller-allocated
  * with src's nblks / nze; dst->row_blk_size/col_blk_size must already hold the
  * swapped size arrays. */
 int dbcsr_amd_bcsr_transpose(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, dbcsr_amd_bcsr* dst, void* stream);
+/* The conjugate transpose (complex_8; for real types the same as dbcsr_amd_bcsr_transpose): what 'C' means in dbcsr_multiply. */
+int dbcsr_amd_bcsr_transpose_conj(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, dbcsr_amd_bcsr* dst, void* stream);
 
 /* Checksums of dbcsr_checksum (src/dist/dbcsr_dist_util.F:432-577) on the
  * device: out[0] = sum x^2, out[1] = sum x*ln|row*col| (1-based global element
- * coordinates).  Synchronises stream. */
+ * coordinates).  Synchronises stream.  Real types only: -10 for complex_8. */
 int dbcsr_amd_bcsr_checksum(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, double* out2, void* stream);
 
 /* Synthetic block values of the reference's test generator
  * (src/ops/dbcsr_test_methods.F:423-429 + LAPACK dlarnv/slarnv idist=1): block b of the
  * index gets larnv(seed(row+1, nblkrows, col+1, nblkcols, counter)).  Used by the
- * benchmark to create inputs directly in HBM. */
+ * benchmark to create inputs directly in HBM.  complex_8: LAPACK zlarnv(idist = 1) -- the block's 2*m*n doubles are the dlarnv stream
+ * of the block's seed, re, im, re, im, ... */
 int dbcsr_amd_bcsr_fill_random(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, int counter, void* stream);
 
 /* Same for one rank's part of a distributed matrix: row_gid/col_gid (device, may be NULL)
@@ -172,6 +196,13 @@ int dbcsr_amd_bcsr_fill_random_dist(void* handle, libsmm_acc_data_t datatype, co
 int dbcsr_amd_multiply(void* handle, char transa, char transb, libsmm_acc_data_t datatype, double alpha, const dbcsr_amd_bcsr* matrix_a,
   const dbcsr_amd_bcsr* matrix_b, double beta, const dbcsr_amd_bcsr* matrix_c, const int64_t* limits, int retain_sparsity,
   double filter_eps, dbcsr_amd_bcsr* c_out, int64_t* flop, void* stream);
+/* The same for complex_8 matrices with complex scalars {re, im}: 'C' is the conjugate transpose, 'T' the plain one; beta == 0 means both
+ * parts are zero; *flop stays sum 2*m*n*k, as the reference counts it for every type.  Complex multiplies run in one pass over k.
+ * (dbcsr_amd_multiply itself keeps answering -10 for dbcsr_type_complex_8, as it always did: hosts written against the real-only
+ * library rely on that answer to leave a complex multiply to the reference path.  This entry is how a complex multiply is asked for.) */
+int dbcsr_amd_multiply_z(void* handle, char transa, char transb, const double alpha[2], const dbcsr_amd_bcsr* matrix_a, const dbcsr_amd_bcsr* matrix_b,
+  const double beta[2], const dbcsr_amd_bcsr* matrix_c, const int64_t* limits, int retain_sparsity, double filter_eps,
+  dbcsr_amd_bcsr* c_out, int64_t* flop, void* stream);
 int dbcsr_amd_bcsr_release(dbcsr_amd_bcsr* m);
 
 /* HIP-event timing of the last dbcsr_amd_mm_numeric call on this handle, taken
@@ -244,7 +275,8 @@ int dbcsr_amd_mm_trust_plan(void* handle, int on);
 /* A filtered multiply (reference: src/mm/dbcsr_mm_multrec.F:373-383 -- the product of a multiply with filter_eps is filtered with the same eps before it is
    finalized): announce the final block filter of the NEXT dbcsr_amd_mm_numeric of this handle.  Its product kernels form a block's squared norm before they write it
    and leave a block with ||blk||^2 < eps^2 UNWRITTEN -- the block filter is going to drop it (same double, same comparison), nobody may read it before.  The C that
-   comes back is therefore only good for dbcsr_amd_bcsr_filter_count / _apply with an eps that is not smaller (a smaller one is refused: -3).  On products with many
+   comes back is therefore only good for dbcsr_amd_bcsr_filter_count / _apply with an eps that is not smaller (a smaller one is refused: -3).  Ignored by
+   complex_8 multiplies (every block is written).  On products with many
    dropped blocks the dropped share of C's write traffic is saved.  Without this call every block is written.  Call it AFTER the symbolic phase of the
    multiply it is meant for (a symbolic phase cancels an announcement that was never consumed).  fp64; ignored for retain_sparsity and in-place accumulation. */
 int dbcsr_amd_mm_expect_filter(void* handle, double eps);
