@@ -101,14 +101,15 @@ int transposed(void* h, libsmm_acc_data_t dt, const dbcsr_amd_bcsr* src, Owned& 
 }
 
 
-// block (r, c) <-> its twin (c, r): mode 1 stored triangle -> canonical form, mode 2 canonical form -> stored triangle (dbcsr_amd_bcsr_twin_*)
-int twin(void* h, libsmm_acc_data_t dt, const dbcsr_amd_bcsr* src, int mode, int antisymmetric, Owned& dst, void* stream) {
+// block (r, c) <-> its twin (c, r): mode 1 stored triangle -> canonical form, mode 2 canonical form -> stored triangle (dbcsr_amd_bcsr_twin_*);
+// kind 0 symmetric, 1 antisymmetric, 2 hermitian, 3 antihermitian
+int twin(void* h, libsmm_acc_data_t dt, const dbcsr_amd_bcsr* src, int mode, int kind, Owned& dst, void* stream) {
   if (alloc_row_p(dst, src->nblkrows)) return -1;
   int64_t nb = 0, nz = 0;
   int rc = dbcsr_amd_bcsr_twin_count(h, src, mode, dst.m.row_p, &nb, &nz, stream);
   if (rc) return rc;
   if (alloc_arrays(dst, src->nblkrows, src->nblkcols, src->row_blk_size, src->col_blk_size, nb, nz, elem_size(dt), false)) return -1;
-  return dbcsr_amd_bcsr_twin_apply(h, dt, src, mode, antisymmetric, &dst.m, stream);
+  return dbcsr_amd_bcsr_twin_apply(h, dt, src, mode, kind, &dst.m, stream);
 }
 
 // sum of the block sizes of one dimension (device array of n int32): dbcsr_nfullrows_total / dbcsr_nfullcols_total
@@ -424,12 +425,11 @@ int dbcsr_amd_multiply_z(void* handle, char transa, char transb, const double al
                       flop, stream);
 }
 
-int dbcsr_amd_bcsr_desymmetrized(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, int antisymmetric, dbcsr_amd_bcsr* dst,
-                                 void* stream) {
-  if (!handle || !src || !dst) return -1;
-  if (datatype != dbcsr_type_real_8 && datatype != dbcsr_type_real_4) return -10;
+int dbcsr_amd_bcsr_desymmetrized(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, int kind, dbcsr_amd_bcsr* dst, void* stream) {
+  if (!handle || !src || !dst || kind < 0 || kind > 3) return -1;
+  if (datatype != dbcsr_type_real_8 && datatype != dbcsr_type_real_4 && datatype != dbcsr_type_complex_8) return -10;
   Owned full;
-  int rc = twin(handle, datatype, src, 0, antisymmetric, full, stream);
+  int rc = twin(handle, datatype, src, 0, kind, full, stream);
   if (rc == 0 && hipStreamSynchronize(stream_of(stream)) != hipSuccess) rc = -1;
   if (rc) return rc;
   *dst = full.m;
@@ -437,38 +437,30 @@ int dbcsr_amd_bcsr_desymmetrized(void* handle, libsmm_acc_data_t datatype, const
   return 0;
 }
 
-int dbcsr_amd_multiply_symmetric_c(void* handle, char transa, char transb, libsmm_acc_data_t datatype, double alpha,
-                                   const dbcsr_amd_bcsr* matrix_a, const dbcsr_amd_bcsr* matrix_b, double beta, const dbcsr_amd_bcsr* matrix_c,
-                                   int antisymmetric, int retain_sparsity, double filter_eps, dbcsr_amd_bcsr* c_out, int64_t* flop, void* stream) {
-  return dbcsr_amd_multiply_symmetric_c_klimits(handle, transa, transb, datatype, alpha, matrix_a, matrix_b, beta, matrix_c, antisymmetric, 0, 0,
-                                                retain_sparsity, filter_eps, c_out, flop, stream);
-}
-
-// ... with limits on the INNER dimension (first_k / last_k of dbcsr_multiply: 1-based inclusive element indices, 0 = not given).  They crop op(A)'s
-// columns and op(B)'s rows and have nothing to do with C's symmetry; the reference's own tests multiply into symmetric products with exactly these
-// (tests/dbcsr_test_multiply.F:196-200: full row / column limits, any k limits).  Row / column limits together with a product with symmetry are not
-// offered (the caller leaves such a multiply to the reference path).
-int dbcsr_amd_multiply_symmetric_c_klimits(void* handle, char transa, char transb, libsmm_acc_data_t datatype, double alpha,
-                                           const dbcsr_amd_bcsr* matrix_a, const dbcsr_amd_bcsr* matrix_b, double beta, const dbcsr_amd_bcsr* matrix_c,
-                                           int antisymmetric, int64_t first_k, int64_t last_k, int retain_sparsity, double filter_eps,
-                                           dbcsr_amd_bcsr* c_out, int64_t* flop, void* stream) {
-  if (!handle || !matrix_c || !c_out || matrix_c->nblkrows != matrix_c->nblkcols) return -1;
+// Product matrix with symmetry (kind 0 symmetric ... 3 antihermitian), limits on the INNER dimension only (first_k / last_k of dbcsr_multiply: 1-based
+// inclusive element indices, 0 = not given).  They crop op(A)'s columns and op(B)'s rows and have nothing to do with C's symmetry; the reference's own tests
+// multiply into symmetric products with exactly these (tests/dbcsr_test_multiply.F:196-200: full row / column limits, any k limits).  Row / column limits
+// together with a product with symmetry are not offered (the caller leaves such a multiply to the reference path).
+static int multiply_symmetric_c_any(void* handle, char transa, char transb, libsmm_acc_data_t datatype, const double alpha[2],
+                                    const dbcsr_amd_bcsr* matrix_a, const dbcsr_amd_bcsr* matrix_b, const double beta[2], const dbcsr_amd_bcsr* matrix_c,
+                                    int kind, int64_t first_k, int64_t last_k, int retain_sparsity, double filter_eps, dbcsr_amd_bcsr* c_out,
+                                    int64_t* flop, void* stream) {
+  if (!handle || !matrix_c || !c_out || matrix_c->nblkrows != matrix_c->nblkcols || kind < 0 || kind > 3) return -1;
   const int64_t limits[6] = {0, 0, 0, 0, first_k, last_k};
-  if (datatype != dbcsr_type_real_8 && datatype != dbcsr_type_real_4) return -10;
   // dbcsr_mm.F:711-719: the index of a product matrix with symmetry is put into canonical form before the multiplication ...
   Owned canon;
-  int rc = twin(handle, datatype, matrix_c, 1, antisymmetric, canon, stream);
+  int rc = twin(handle, datatype, matrix_c, 1, kind, canon, stream);
   if (rc) return rc;
   // ... the local multiply computes only the blocks stored in that form (dbcsr_mm_csr.F:280-292) ...
   dbcsr_amd_bcsr prod;
   if ((rc = dbcsr_amd_mm_set_canonical_product(handle, 1))) return rc;
-  rc = dbcsr_amd_multiply(handle, transa, transb, datatype, alpha, matrix_a, matrix_b, beta, &canon.m, (first_k || last_k) ? limits : nullptr,
-                          retain_sparsity, filter_eps, &prod, flop, stream);
+  rc = multiply_any(handle, transa, transb, datatype, alpha, matrix_a, matrix_b, beta, &canon.m, (first_k || last_k) ? limits : nullptr, retain_sparsity,
+                    filter_eps, &prod, flop, stream);
   (void)dbcsr_amd_mm_set_canonical_product(handle, 0);
   if (rc) return rc;
   // ... and the result goes back to the stored triangle (row <= column)
   Owned upper;
-  rc = twin(handle, datatype, &prod, 2, antisymmetric, upper, stream);
+  rc = twin(handle, datatype, &prod, 2, kind, upper, stream);
   if (rc == 0 && hipStreamSynchronize(stream_of(stream)) != hipSuccess) rc = -1;
   (void)dbcsr_amd_bcsr_release(&prod);
   if (rc) return rc;
@@ -477,6 +469,33 @@ int dbcsr_amd_multiply_symmetric_c_klimits(void* handle, char transa, char trans
   c_out->col_blk_size = matrix_c->col_blk_size;
   upper.live = false;
   return 0;
+}
+
+int dbcsr_amd_multiply_symmetric_c(void* handle, char transa, char transb, libsmm_acc_data_t datatype, double alpha,
+                                   const dbcsr_amd_bcsr* matrix_a, const dbcsr_amd_bcsr* matrix_b, double beta, const dbcsr_amd_bcsr* matrix_c,
+                                   int kind, int retain_sparsity, double filter_eps, dbcsr_amd_bcsr* c_out, int64_t* flop, void* stream) {
+  return dbcsr_amd_multiply_symmetric_c_klimits(handle, transa, transb, datatype, alpha, matrix_a, matrix_b, beta, matrix_c, kind, 0, 0,
+                                                retain_sparsity, filter_eps, c_out, flop, stream);
+}
+
+int dbcsr_amd_multiply_symmetric_c_klimits(void* handle, char transa, char transb, libsmm_acc_data_t datatype, double alpha,
+                                           const dbcsr_amd_bcsr* matrix_a, const dbcsr_amd_bcsr* matrix_b, double beta, const dbcsr_amd_bcsr* matrix_c,
+                                           int kind, int64_t first_k, int64_t last_k, int retain_sparsity, double filter_eps,
+                                           dbcsr_amd_bcsr* c_out, int64_t* flop, void* stream) {
+  if (!handle || !matrix_c || !c_out || matrix_c->nblkrows != matrix_c->nblkcols || kind < 0 || kind > 3) return -1;
+  // (complex_8 keeps its -10 in the entries with real scalars, as in dbcsr_amd_multiply: a complex product is asked for by name, ..._symmetric_c_z)
+  if (datatype != dbcsr_type_real_8 && datatype != dbcsr_type_real_4) return -10;
+  const double al[2] = {alpha, 0.0}, be[2] = {beta, 0.0};
+  return multiply_symmetric_c_any(handle, transa, transb, datatype, al, matrix_a, matrix_b, be, matrix_c, kind, first_k, last_k, retain_sparsity, filter_eps,
+                                  c_out, flop, stream);
+}
+
+int dbcsr_amd_multiply_symmetric_c_z(void* handle, char transa, char transb, const double alpha[2], const dbcsr_amd_bcsr* matrix_a,
+                                     const dbcsr_amd_bcsr* matrix_b, const double beta[2], const dbcsr_amd_bcsr* matrix_c, int kind, int64_t first_k,
+                                     int64_t last_k, int retain_sparsity, double filter_eps, dbcsr_amd_bcsr* c_out, int64_t* flop, void* stream) {
+  if (!alpha || !beta) return -1;
+  return multiply_symmetric_c_any(handle, transa, transb, dbcsr_type_complex_8, alpha, matrix_a, matrix_b, beta, matrix_c, kind, first_k, last_k,
+                                  retain_sparsity, filter_eps, c_out, flop, stream);
 }
 
 }  // extern "C"

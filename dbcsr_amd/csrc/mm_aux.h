@@ -251,7 +251,7 @@ template <typename T>
 __global__ void __launch_bounds__(256)
 desym_fill(const int* __restrict__ s_row_p, const int* __restrict__ s_col_i, const int64_t* __restrict__ s_blk_p, const T* __restrict__ s_data,
            const int* __restrict__ sizes, const uint32_t* __restrict__ bm, const int* __restrict__ pre, const int* __restrict__ d_row_p,
-           const int64_t* __restrict__ d_blk_p_ws, int nbr, int W, T sign, int mode, int* __restrict__ d_col_i, int64_t* __restrict__ d_blk_p,
+           const int64_t* __restrict__ d_blk_p_ws, int nbr, int W, int kind, int mode, int* __restrict__ d_col_i, int64_t* __restrict__ d_blk_p,
            T* __restrict__ d_data) {
   const int lane = threadIdx.x & 63;
   const int r = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -284,7 +284,101 @@ desym_fill(const int* __restrict__ s_row_p, const int* __restrict__ s_col_i, con
       T* d1 = d_data + d_blk_p_ws[t1];
       for (int e = lane; e < m * n; e += 64) {
         const int i = e % m, j = e / m;  // src(i, j) -> dst(j, i), dst is n x m
-        d1[j + (size_t)n * i] = sign * src[e];
+        d1[j + (size_t)n * i] = twin_of(src[e], kind);
+      }
+    }
+  }
+}
+
+// The same for complex_8 (16-byte elements), the twin going through a per-wave LDS image so that BOTH global sides are contiguous: in desym_fill the twin's
+// store is strided by n elements per lane, here a lane loads one element of a run of the source, puts it at its transposed place in the image, reads
+// the image in the order of the destination and stores to consecutive addresses (measured against desym_fill<z64> on the stored triangle of a 32768^2
+// matrix at 10 % fill: 1.85 against 2.13 ms with 23 x 23 blocks, 1.92 against 2.20 ms with 32 x 32, profiles/hermitian_twin.txt).  The image holds a
+// square piece of kTwinEdge x kTwinEdge elements with an odd column pitch (the convention of mm_numeric_z64.h: the granule of a lane is a whole element,
+// so 33 elements between neighbouring lanes spread a 16-byte store over all banks); a larger block is walked piece by piece.  Up to four loads are in
+// flight per lane before the first LDS store.  A wave's LDS operations complete in order, and the image belongs to one wave: no barrier.  The copy of a
+// block that stays is taken from the same loads.
+constexpr int kTwinEdge = 32, kTwinPitch = kTwinEdge + 1;
+__global__ void __launch_bounds__(256)
+twin_fill_z64(const int* __restrict__ s_row_p, const int* __restrict__ s_col_i, const int64_t* __restrict__ s_blk_p, const z64* __restrict__ s_data,
+              const int* __restrict__ sizes, const uint32_t* __restrict__ bm, const int* __restrict__ pre, const int* __restrict__ d_row_p,
+              const int64_t* __restrict__ d_blk_p_ws, int nbr, int W, int kind, int mode, int* __restrict__ d_col_i, int64_t* __restrict__ d_blk_p,
+              z64* __restrict__ d_data) {
+  typedef double f64x2 __attribute__((ext_vector_type(2)));
+  __shared__ f64x2 images[4][kTwinEdge * kTwinPitch];
+  const int lane = threadIdx.x & 63;
+  const int r = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (r >= nbr) return;
+  f64x2* img = images[__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))];
+  const int m = sizes[r];
+  const bool neg_re = kind & 1, neg_im = ((kind >> 1) ^ kind) & 1;   // twin_of(z64, kind)
+  auto slot = [&](int row, int col) {
+    const uint32_t wv = bm[(size_t)row * W + (col >> 5)];
+    return d_row_p[row] + pre[(size_t)row * W + (col >> 5)] + __popc(wv & ((1u << (col & 31)) - 1u));
+  };
+  for (int b = s_row_p[r]; b < s_row_p[r + 1]; ++b) {
+    const int c = s_col_i[b];
+    const int n = sizes[c];
+    const f64x2* src = reinterpret_cast<const f64x2*>(s_data + s_blk_p[b]);
+    const bool stay = mode == 0 || !twin_moves(mode, r, c), go = mode == 0 ? c != r : twin_moves(mode, r, c);
+    f64x2* d0 = nullptr;
+    if (stay) {
+      const int t0 = slot(r, c);
+      if (lane == 0) {
+        d_col_i[t0] = c;
+        d_blk_p[t0] = d_blk_p_ws[t0];
+      }
+      d0 = reinterpret_cast<f64x2*>(d_data + d_blk_p_ws[t0]);
+    }
+    if (!go) {
+      for (int e = lane; e < m * n; e += 64) d0[e] = src[e];
+      continue;
+    }
+    const int t1 = slot(c, r);
+    if (lane == 0) {
+      d_col_i[t1] = r;
+      d_blk_p[t1] = d_blk_p_ws[t1];
+    }
+    f64x2* d1 = reinterpret_cast<f64x2*>(d_data + d_blk_p_ws[t1]);
+    // src is m x n, its twin n x m: piece (i0 ... i0 + pm, j0 ... j0 + pn) of src becomes piece (j0 ..., i0 ...) of the twin
+    for (int j0 = 0; j0 < n; j0 += kTwinEdge) {
+      const int pn = n - j0 < kTwinEdge ? n - j0 : kTwinEdge;
+      for (int i0 = 0; i0 < m; i0 += kTwinEdge) {
+        const int pm = m - i0 < kTwinEdge ? m - i0 : kTwinEdge;
+        const int cnt = pm * pn;
+        // element t of the piece in source order is (i, j) = (t % pm, t / pm); t advances by 64 per step: (i, j) by (64 % pm, 64 / pm) with a carry
+        int i = lane % pm, j = lane / pm;
+        const int si = 64 % pm, sj = 64 / pm;
+        for (int t = lane; t < cnt + lane; t += 256) {   // (the bound is wave-uniform: t - lane < cnt)
+          f64x2 v[4];
+          int at[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            at[u] = -1;
+            if (t + 64 * u < cnt) {
+              const size_t e = (size_t)(i0 + i) + (size_t)m * (j0 + j);
+              v[u] = src[e];
+              if (stay) d0[e] = v[u];
+              at[u] = j + kTwinPitch * i;
+            }
+            i += si, j += sj;
+            if (i >= pm) i -= pm, ++j;
+          }
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+            if (at[u] >= 0) img[at[u]] = v[u];
+        }
+        // element t of the piece in the twin's order is (j, i) = (t % pn, t / pn)
+        int jj = lane % pn, ii = lane / pn;
+        const int sjj = 64 % pn, sii = 64 / pn;
+        for (int t = lane; t < cnt; t += 64) {
+          f64x2 v = img[jj + kTwinPitch * ii];
+          if (neg_re) v[0] = -v[0];
+          if (neg_im) v[1] = -v[1];
+          d1[(size_t)(j0 + jj) + (size_t)n * (i0 + ii)] = v;
+          jj += sjj, ii += sii;
+          if (jj >= pn) jj -= pn, ++ii;
+        }
       }
     }
   }

@@ -26,5 +26,12 @@ __device__ __forceinline__ double conj_of(double x) { return x; }
 __device__ __forceinline__ float conj_of(float x) { return x; }
 __device__ __forceinline__ z64 conj_of(z64 x) { return z64(x.re, -x.im); }
 
+// element of the twin block of a matrix with symmetry (dbcsr_amd_bcsr_twin_apply; the transposition is the caller's).  kind: bit 0 negates, bit 1
+// conjugates -- 0 symmetric, 1 antisymmetric, 2 hermitian, 3 antihermitian.  Sign flips only: exact, and an involution bit for bit.  Real data: conjugation
+// is the identity
+__device__ __forceinline__ double twin_of(double x, int kind) { return (kind & 1) ? -x : x; }
+__device__ __forceinline__ float twin_of(float x, int kind) { return (kind & 1) ? -x : x; }
+__device__ __forceinline__ z64 twin_of(z64 x, int kind) { return z64((kind & 1) ? -x.re : x.re, (((kind >> 1) ^ kind) & 1) ? -x.im : x.im); }
+
 }  // namespace dbcsr_amd
 #endif

@@ -38,7 +38,11 @@ MM_SYMBOLS = [
     "dbcsr_amd_bcsr_filter_apply_index", "dbcsr_amd_mm_set_filter_in_place",
     # complex_8: complex scalars as double[2] = {re, im}
     "dbcsr_amd_mm_numeric_z", "dbcsr_amd_mm_init_c_z", "dbcsr_amd_bcsr_scale_window_z", "dbcsr_amd_bcsr_transpose_conj", "dbcsr_amd_multiply_z",
+    "dbcsr_amd_multiply_symmetric_c_z",
 ]
+
+# `kind` of a matrix with symmetry in the C ABI (include/dbcsr_amd_mm.h): bit 0 negates the twin block, bit 1 conjugates it
+SYMMETRY_KIND = {"S": 0, "A": 1, "H": 2, "K": 3}
 
 
 COMM_SYMBOLS = ["dbcsr_amd_comm_available", "dbcsr_amd_comm_unique_id", "dbcsr_amd_comm_create", "dbcsr_amd_comm_destroy", "dbcsr_amd_comm_rank", "dbcsr_amd_comm_exchange",
@@ -179,6 +183,7 @@ def load_library(lab=False):
     L.dbcsr_amd_bcsr_scale_window_z.argtypes = [vp, BP, Z, i64, i64, i64, i64, vp]
     L.dbcsr_amd_bcsr_transpose_conj.argtypes = [vp, i32, BP, BP, vp]
     L.dbcsr_amd_multiply_z.argtypes = [vp, C.c_char, C.c_char, Z, BP, BP, Z, BP, C.POINTER(i64), i32, C.c_double, BP, C.POINTER(i64), vp]
+    L.dbcsr_amd_multiply_symmetric_c_z.argtypes = [vp, C.c_char, C.c_char, Z, BP, BP, Z, BP, i32, i64, i64, i32, C.c_double, BP, C.POINTER(i64), vp]
     if lab:   # diagnostics of the experimental dataflows (dbcsr_amd/csrc/mm_lab_api.h): the shipping build does not export them
         L.dbcsr_amd_mm_tile_stats.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
         L.dbcsr_amd_mm_band_stats.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]

@@ -22,6 +22,20 @@ def _dtype_code(dt):
     raise TypeError("dbcsr_amd supports real_8 (float64), real_4 (float32) and complex_8 (complex128) data, got %r" % (dt,))
 
 
+def symmetry_kind(symmetry, dtype):
+    """The C ABI's `kind` (lib.SYMMETRY_KIND) of a matrix type with symmetry, checked against the data type -- the one place that says which
+    symmetries the Python mirror offers.  Real data: 'S' / 'A' (anything else: ValueError); complex data: 'H' / 'K' ('S' / 'A' of complex
+    matrices are not offered here yet: NotImplementedError, anything else: ValueError)."""
+    if dtype.is_complex:
+        if symmetry in ("S", "A"):
+            raise NotImplementedError("complex matrices with symmetry %r (complex data: 'N', 'H', 'K')" % (symmetry,))
+        if symmetry not in ("H", "K"):
+            raise ValueError("unsupported matrix symmetry %r (complex data: 'N', 'H', 'K')" % (symmetry,))
+    elif symmetry not in ("S", "A"):
+        raise ValueError("unsupported matrix symmetry %r (real data: 'N', 'S', 'A')" % (symmetry,))
+    return _lib.SYMMETRY_KIND[symmetry]
+
+
 class StreamHandle:
     """The C-ABI stream convention: a pointer to a hipStream_t (dbcsr_acc.h)."""
 
@@ -59,8 +73,9 @@ class DbcsrMatrix:
         self.row_blk_size, self.col_blk_size = row_blk_size, col_blk_size
         self.row_p, self.col_i, self.blk_p, self.data = row_p, col_i, blk_p, data
         self.name = name
-        # matrix_type of the reference (src/core/dbcsr_types.F): 'N' no symmetry, 'S' symmetric, 'A' antisymmetric -- the latter
-        # two store one block per symmetric pair
+        # matrix_type of the reference (src/core/dbcsr_types.F): 'N' no symmetry, 'S' symmetric, 'A' antisymmetric, 'H' hermitian,
+        # 'K' antihermitian -- all but 'N' store one block per pair (r, c) / (c, r).  Checked where it is used (symmetry_kind): real data
+        # takes 'S' / 'A', complex data 'H' / 'K'
         self.symmetry = symmetry
         # number of elements the index refers to when that is not the whole data area (see nze); None: all of it
         self._nze = None if nze is None else int(nze)
@@ -108,6 +123,10 @@ class DbcsrMatrix:
     def packed(self):
         """The index refers to every element of the data area (no holes left by dropped blocks)."""
         return self.nze == int(self.data.numel())
+
+    def symmetry_kind(self):
+        """The C ABI's `kind` of this matrix's symmetry: symmetry_kind(self.symmetry, self.dtype)."""
+        return symmetry_kind(self.symmetry, self.dtype)
 
     def adopt(self, other):
         """Takes over other's index arrays, data area and element count (the sizes stay): how a multiply hands its result to matrix_c."""

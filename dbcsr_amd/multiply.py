@@ -13,7 +13,7 @@ import os
 import torch
 
 from . import lib as _lib
-from .matrix import DbcsrMatrix, StreamHandle
+from .matrix import DbcsrMatrix, StreamHandle, symmetry_kind
 
 dbcsr_no_transpose = "N"
 dbcsr_transpose = "T"
@@ -284,14 +284,11 @@ class MultiplyEngine:
         self.filter_in_place = bool(on)
 
     def desymmetrized(self, M, stream=None):
-        """Full matrix of a symmetric ('S') / antisymmetric ('A') operand (dbcsr_desymmetrize_deep, done by the reference while
-        it builds the multiplication images, dbcsr_mm_cannon.F:284, 351-379)."""
+        """Full matrix of a symmetric ('S') / antisymmetric ('A') real or hermitian ('H') / antihermitian ('K') complex operand
+        (dbcsr_desymmetrize_deep, done by the reference while it builds the multiplication images, dbcsr_mm_cannon.F:284, 351-379)."""
         if M.symmetry == "N":
             return M
-        if M.dtype.is_complex:
-            raise NotImplementedError("complex matrices with symmetry %r (hermitian / antihermitian matrices are not offered yet)" % (M.symmetry,))
-        if M.symmetry not in ("S", "A"):
-            raise ValueError("unsupported matrix symmetry %r (real data: 'N', 'S', 'A')" % (M.symmetry,))
+        kind = symmetry_kind(M.symmetry, M.dtype)
         st = StreamHandle(stream)
         src = M.desc()
         row_p = torch.empty(M.nblkrows + 1, dtype=torch.int32, device=M.row_p.device)
@@ -303,15 +300,18 @@ class MultiplyEngine:
         out = DbcsrMatrix(M.row_blk_size, M.col_blk_size, row_p, torch.empty(nb.value, dtype=torch.int32, device=dev),
                           torch.empty(nb.value, dtype=torch.int64, device=dev), torch.empty(nz.value, dtype=M.dtype, device=dev), M.name)
         d = out.desc(out=True)
-        rc = self.L.dbcsr_amd_bcsr_desymmetrize_apply(self.h, M.dtype_code, C.byref(src), 1 if M.symmetry == "A" else 0, C.byref(d), st.ptr)
+        rc = self.L.dbcsr_amd_bcsr_desymmetrize_apply(self.h, M.dtype_code, C.byref(src), kind, C.byref(d), st.ptr)
         if rc != 0:
             raise RuntimeError("dbcsr_amd_bcsr_desymmetrize_apply failed (%d)" % rc)
         return out
 
     def twin_moved(self, M, mode, symmetry, stream=None):
-        """Blocks of a matrix with symmetry moved to their twins (r, c) -> (c, r), transposed (negated when antisymmetric):
-        mode 1 = stored triangle -> canonical (checkerboard) form (dbcsr_make_index_canonical), mode 2 = canonical form -> stored
-        triangle (row <= column).  include/dbcsr_amd_mm.h: dbcsr_amd_bcsr_twin_count / _apply."""
+        """Blocks of a matrix with symmetry moved to their twins (r, c) -> (c, r): transposed, negated when symmetry is 'A' / 'K',
+        conjugated when it is 'H' / 'K'.  mode 1 = stored triangle -> canonical (checkerboard) form (dbcsr_make_index_canonical), mode 2 = canonical form -> stored
+        triangle (row <= column).  include/dbcsr_amd_mm.h: dbcsr_amd_bcsr_twin_count / _apply.  The C ABI's primitive: any of the four
+        symmetries with any data type (what dbcsr_multiply offers is decided by matrix.symmetry_kind)."""
+        if symmetry not in _lib.SYMMETRY_KIND:
+            raise ValueError("unsupported matrix symmetry %r ('S', 'A', 'H', 'K')" % (symmetry,))
         st = StreamHandle(stream)
         src = M.desc()
         dev = M.row_p.device
@@ -323,7 +323,7 @@ class MultiplyEngine:
         out = DbcsrMatrix(M.row_blk_size, M.col_blk_size, row_p, torch.empty(nb.value, dtype=torch.int32, device=dev),
                           torch.empty(nb.value, dtype=torch.int64, device=dev), torch.empty(nz.value, dtype=M.dtype, device=dev), M.name)
         d = out.desc(out=True)
-        rc = self.L.dbcsr_amd_bcsr_twin_apply(self.h, M.dtype_code, C.byref(src), mode, 1 if symmetry == "A" else 0, C.byref(d), st.ptr)
+        rc = self.L.dbcsr_amd_bcsr_twin_apply(self.h, M.dtype_code, C.byref(src), mode, _lib.SYMMETRY_KIND[symmetry], C.byref(d), st.ptr)
         if rc != 0:
             raise RuntimeError("dbcsr_amd_bcsr_twin_apply failed (%d)" % rc)
         return out
@@ -564,15 +564,15 @@ def dbcsr_multiply(transa, transb, alpha, matrix_a, matrix_b, beta, matrix_c, fi
     E = engine or default_engine()
     c_symm = getattr(matrix_c, "symmetry", "N")
     cplx = matrix_c.dtype.is_complex
-    if cplx and any(getattr(m, "symmetry", "N") != "N" for m in (matrix_a, matrix_b, matrix_c)):
-        raise NotImplementedError("dbcsr_multiply: complex matrices with symmetry (hermitian / antihermitian matrices are not offered yet)")
+    for m in (matrix_a, matrix_b, matrix_c):   # real data: 'S' / 'A'; complex data: 'H' / 'K' ('S' / 'A' not offered yet)
+        if getattr(m, "symmetry", "N") != "N":
+            symmetry_kind(m.symmetry, m.dtype)
     if not cplx and (isinstance(alpha, complex) or isinstance(beta, complex)):
         raise TypeError("dbcsr_multiply: complex scalars with real matrices")
     if c_symm != "N":
         # Product matrix with symmetry (src/mm/dbcsr_mm.F:711-719): its index goes into canonical (checkerboard) form, only the blocks
         # stored in that form are computed (dbcsr_mm_csr.F:280-292), the result goes back to the stored triangle (row <= column).
-        if c_symm not in ("S", "A"):
-            raise ValueError("unsupported matrix symmetry %r (real data: 'N', 'S', 'A')" % (c_symm,))
+        # A stored block that moves in canonical form is therefore updated through its twin: X <- twin(beta * twin(X) + alpha * P(c, r)).
         if any(v is not None and v != 0 for v in (first_row, last_row, first_column, last_column, first_k, last_k)):
             raise NotImplementedError("dbcsr_multiply: limits with a symmetric product matrix (the reference's tests run full limits only)")
         canon = E.twin_moved(matrix_c, 1, c_symm)

@@ -22,10 +22,11 @@
  * Data types: dbcsr_type_real_8, dbcsr_type_real_4 and dbcsr_type_complex_8 (COMPLEX(real_8): (re, im) pairs of doubles,
  * interleaved; an element offset in blk_p counts complex elements).  Every entry with a datatype argument takes complex_8 unless
  * it says otherwise below; the entries whose scalars are real doubles read them as x + 0i for complex data, and the _z entries
- * take complex scalars as const double[2] = {re, im}.  NOT offered for complex_8 (they return -10, as every entry does for
- * dbcsr_type_complex_4): libsmm_acc_process / _transpose (the reference's accelerator path returns -10 for complex stacks too),
- * matrices with symmetry (dbcsr_amd_bcsr_twin_*, _desymmetrize_*, _desymmetrized, dbcsr_amd_multiply_symmetric_c*: hermitian and
- * antihermitian matrices are a follow-up), dbcsr_amd_bcsr_checksum, and dbcsr_amd_multiply (see dbcsr_amd_multiply_z).
+ * take complex scalars as const double[2] = {re, im}.  Matrices with symmetry: all four kinds (symmetric, antisymmetric, hermitian, antihermitian;
+ * dbcsr_amd_bcsr_twin_*, _desymmetrize_*, _desymmetrized) for every type, and a complex_8 product matrix with symmetry through
+ * dbcsr_amd_multiply_symmetric_c_z.  NOT offered for complex_8 (they return -10, as every entry does for dbcsr_type_complex_4): libsmm_acc_process /
+ * _transpose (the reference's accelerator path returns -10 for complex stacks too), dbcsr_amd_bcsr_checksum, and the multiplies with real scalars,
+ * dbcsr_amd_multiply and dbcsr_amd_multiply_symmetric_c / _klimits (see dbcsr_amd_multiply_z and dbcsr_amd_multiply_symmetric_c_z).
  *
  * Return: 0 ok, non-zero error (message on stderr).  Streams use the handle
  * convention of dbcsr_acc.h (pointer to hipStream_t, NULL = null stream).
@@ -212,41 +213,53 @@ int dbcsr_amd_bcsr_release(dbcsr_amd_bcsr* m);
 int dbcsr_amd_mm_timing(void* handle, float* ms_fill, float* ms_numeric);
 
 /* Symbol name of the dominant kernel, for profile look-up. */
-/* Symmetric operands (src/core/dbcsr_types.F: matrix_type 'S' / 'A'; the reference desymmetrizes them while it builds the
- * multiplication images, src/mm/dbcsr_mm_cannon.F:284, 351-379): src holds ONE block per symmetric pair (any mix of upper and
- * lower blocks, square block structure); the full matrix gets block (c, r) = +block(r, c)^T (symmetric) or -block(r, c)^T
- * (antisymmetric) in addition.  _count writes dst_row_p [nblkrows+1] (device) and the block / element counts (host,
- * synchronises); _apply fills caller-allocated dst arrays (dst->row_p = that row_p), blocks packed in index order. */
+/* Matrices with symmetry (src/core/dbcsr_types.F: matrix_type 'S' symmetric, 'A' antisymmetric, 'H' hermitian, 'K' antihermitian): square block
+ * structure, ONE block stored per pair (r, c) / (c, r), diagonal blocks stored in full and taken as they are (nobody checks that they have the symmetry).
+ * The twin at (c, r) of a stored block X at (r, c), r != c, by `kind`:
+ *     0 symmetric      X^T           1 antisymmetric  -X^T
+ *     2 hermitian      conj(X)^T     3 antihermitian  -conj(X)^T
+ * (bit 0 negates, bit 1 conjugates; sign flips and copies: every result below is defined bit for bit; any other value: -1).  Real data: conjugation is the
+ * identity, kinds 2 / 3 behave as 0 / 1.  All data types, complex_8 with all four kinds.
+ *
+ * Operands (the reference desymmetrizes them while it builds the multiplication images, src/mm/dbcsr_mm_cannon.F:284, 351-379): src holds one block per
+ * pair (any mix of upper and lower blocks); the full matrix gets block (c, r) = twin(block (r, c)) in addition.  _count writes dst_row_p [nblkrows+1]
+ * (device) and the block / element counts (host, synchronises); _apply fills caller-allocated dst arrays (dst->row_p = that row_p), blocks packed in index
+ * order.  An operand is desymmetrized BEFORE op() is applied: 'N', 'T' and 'C' all stay meaningful for a hermitian operand. */
 int dbcsr_amd_bcsr_desymmetrize_count(void* handle, const dbcsr_amd_bcsr* src, int32_t* dst_row_p, int64_t* nblks, int64_t* nze, void* stream);
-int dbcsr_amd_bcsr_desymmetrize_apply(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, int antisymmetric,
-  dbcsr_amd_bcsr* dst, void* stream);
+int dbcsr_amd_bcsr_desymmetrize_apply(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, int kind, dbcsr_amd_bcsr* dst, void* stream);
 
-/* Product matrix WITH symmetry (matrix_type 'S' / 'A' of matrix_c).  The reference puts the index of such a product matrix into
- * canonical (checkerboard) form before the multiplication (src/mm/dbcsr_mm.F:711-719, dbcsr_make_index_canonical), its local
- * multiply computes block (i, j) only when that is the stored one of the pair (i, j) / (j, i) (src/mm/dbcsr_mm_csr.F:280-292,
- * checker_tr of src/dist/dbcsr_dist_operations.F:65-75), and the result is returned as the stored triangle.  The pieces:
- *   dbcsr_amd_bcsr_twin_{count,apply}  mode 0: desymmetrize (= the two calls above); mode 1: stored triangle (row <= column) ->
- *     canonical form; mode 2: canonical form -> stored triangle.  A block that changes sides is transposed (negated when
- *     antisymmetric).  Same calling convention as desymmetrize_{count,apply}.
- *   dbcsr_amd_mm_set_canonical_product(handle, 1): the following symbolic phases of this handle leave out the products of
- *     blocks that are not stored in canonical form (blocks of C_in are kept wherever they are); 0 switches it off again.
- *   dbcsr_amd_multiply_symmetric_c: the whole sequence in one call; matrix_c and c_out hold the stored triangle (row <= column),
- *     no limits (the reference's own tests run symmetric products with full limits only, tests/dbcsr_test_multiply.F:196-200). */
+/* Product matrix WITH symmetry.  The reference puts the index of such a product matrix into canonical (checkerboard) form before the multiplication
+ * (src/mm/dbcsr_mm.F:711-719, dbcsr_make_index_canonical), its local multiply computes block (i, j) only when that is the stored one of the pair
+ * (i, j) / (j, i) (src/mm/dbcsr_mm_csr.F:280-292, checker_tr of src/dist/dbcsr_dist_operations.F:65-75), and the result is returned as the stored
+ * triangle.  The pieces:
+ *   dbcsr_amd_bcsr_twin_{count,apply}  mode 0: desymmetrize (= the two calls above); mode 1: stored triangle (row <= column) -> canonical form; mode 2:
+ *     canonical form -> stored triangle.  A block that changes sides becomes its twin.  Same calling convention as desymmetrize_{count,apply}.
+ *   dbcsr_amd_mm_set_canonical_product(handle, 1): the following symbolic phases of this handle leave out the products of blocks that are not stored in
+ *     canonical form (blocks of C_in are kept wherever they are); 0 switches it off again.
+ *   dbcsr_amd_multiply_symmetric_c: the whole sequence in one call; matrix_c and c_out hold the stored triangle (row <= column), no limits (the
+ *     reference's own tests run symmetric products with full limits only, tests/dbcsr_test_multiply.F:196-200).
+ * With P = op(A) * op(B), a stored block X at (r, c) therefore becomes beta * X + alpha * P(r, c) when it stays where it is in canonical form, and
+ * twin(beta * twin(X) + alpha * P(c, r)) when it moves -- hermitian: conj(beta) * X + conj(alpha) * conj(P(c, r))^T.  Both agree when P has the symmetry
+ * and alpha, beta are real (the caller's contract, as for real data); for other inputs this formula IS what the call computes. */
 /* desymmetrize in one call: dst's arrays are allocated by the library (dbcsr_amd_bcsr_release frees them), size arrays borrowed from src */
-int dbcsr_amd_bcsr_desymmetrized(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, int antisymmetric, dbcsr_amd_bcsr* dst,
-  void* stream);
+int dbcsr_amd_bcsr_desymmetrized(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, int kind, dbcsr_amd_bcsr* dst, void* stream);
 int dbcsr_amd_bcsr_twin_count(void* handle, const dbcsr_amd_bcsr* src, int mode, int32_t* dst_row_p, int64_t* nblks, int64_t* nze, void* stream);
-int dbcsr_amd_bcsr_twin_apply(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, int mode, int antisymmetric,
-  dbcsr_amd_bcsr* dst, void* stream);
+int dbcsr_amd_bcsr_twin_apply(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, int mode, int kind, dbcsr_amd_bcsr* dst,
+  void* stream);
 int dbcsr_amd_mm_set_canonical_product(void* handle, int on);
+/* (real scalars: dbcsr_type_real_8 / _real_4; -10 for complex_8, whose entry is dbcsr_amd_multiply_symmetric_c_z) */
 int dbcsr_amd_multiply_symmetric_c(void* handle, char transa, char transb, libsmm_acc_data_t datatype, double alpha,
-  const dbcsr_amd_bcsr* matrix_a, const dbcsr_amd_bcsr* matrix_b, double beta, const dbcsr_amd_bcsr* matrix_c, int antisymmetric,
+  const dbcsr_amd_bcsr* matrix_a, const dbcsr_amd_bcsr* matrix_b, double beta, const dbcsr_amd_bcsr* matrix_c, int kind,
   int retain_sparsity, double filter_eps, dbcsr_amd_bcsr* c_out, int64_t* flop, void* stream);
 /* the same with limits on the inner dimension (dbcsr_multiply's first_k / last_k: 1-based inclusive element indices, 0 = not given) -- what the
    reference's own tests of products with symmetry use (tests/dbcsr_test_multiply.F:196-200: full row / column limits, any k limits) */
 int dbcsr_amd_multiply_symmetric_c_klimits(void* handle, char transa, char transb, libsmm_acc_data_t datatype, double alpha,
-  const dbcsr_amd_bcsr* matrix_a, const dbcsr_amd_bcsr* matrix_b, double beta, const dbcsr_amd_bcsr* matrix_c, int antisymmetric,
+  const dbcsr_amd_bcsr* matrix_a, const dbcsr_amd_bcsr* matrix_b, double beta, const dbcsr_amd_bcsr* matrix_c, int kind,
   int64_t first_k, int64_t last_k, int retain_sparsity, double filter_eps, dbcsr_amd_bcsr* c_out, int64_t* flop, void* stream);
+/* ... for complex_8 matrices with complex scalars {re, im}: the three steps around dbcsr_amd_multiply_z ('C' conjugates); first_k / last_k as above */
+int dbcsr_amd_multiply_symmetric_c_z(void* handle, char transa, char transb, const double alpha[2], const dbcsr_amd_bcsr* matrix_a,
+  const dbcsr_amd_bcsr* matrix_b, const double beta[2], const dbcsr_amd_bcsr* matrix_c, int kind, int64_t first_k, int64_t last_k,
+  int retain_sparsity, double filter_eps, dbcsr_amd_bcsr* c_out, int64_t* flop, void* stream);
 
 /* Statistics of the last dbcsr_amd_mm_numeric of this handle, by (m, n, k): at most max_entries records are written to
  * `out` (host memory), *n_entries receives the number of distinct triples (larger than max_entries = truncated).
