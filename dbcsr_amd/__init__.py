@@ -6,5 +6,6 @@ Host side (Python) above the C-ABI shared library ``libdbcsr_acc_amd.so``
 :mod:`dbcsr_amd.lib` raises if the native library is missing.
 """
 from .lib import load_library, library_path  # noqa: F401
+from .operations import dbcsr_add, dbcsr_add_on_diag, dbcsr_dot, dbcsr_frobenius_norm, dbcsr_scale, dbcsr_trace  # noqa: F401
 
-__all__ = ["load_library", "library_path"]
+__all__ = ["load_library", "library_path", "dbcsr_add", "dbcsr_scale", "dbcsr_add_on_diag", "dbcsr_trace", "dbcsr_dot", "dbcsr_frobenius_norm"]

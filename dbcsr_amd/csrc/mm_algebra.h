@@ -1,0 +1,401 @@
+// mm_algebra.h -- matrix algebra between multiplies (src/ops/dbcsr_operations.F: dbcsr_add, dbcsr_add_on_diag, dbcsr_trace, dbcsr_dot,
+// dbcsr_frobenius_norm): the union pattern of two matrices, the numeric add per block and flat, the diagonal helpers and the reductions.
+// Part of the device-resident multiply engine: included by mm_engine.hip after mm_aux.h.
+//
+// Every kernel goes by the index (row_p, col_i, blk_p), never by the extent of a data area: an operand may have holes (the result of an in-place filter).
+// ASSUMPTION, shared with the symbolic phase (fill_products / emit_index look a block of C_in up the same way): the block columns of a block row are
+// stored in ascending order, so the position of block (i, j) inside row i is the number of blocks of that row with a column below j -- the bitmap rank
+// row_p[i] + pre[i][j / 32] + popc(word & below) of the add, the binary search of the dot.  Every matrix this library makes has that order.
+//
+// All of them stream memory: 16-byte accesses where the addresses allow (a block of a matrix with 1 x 1 or odd blocks starts at any element), enough waves
+// per block row (row_split) to fill the chip, no atomics on data, no floating-point atomics at all -- the reductions write one partial per wave and
+// checksum_final (mm_aux.h) sums the partials in a fixed order, so a result is the same bits on every call.
+#ifndef DBCSR_AMD_MM_ALGEBRA_H
+#define DBCSR_AMD_MM_ALGEBRA_H
+#include "mm_complex.h"
+#include "mm_epilogue.h"  // wave_sum
+
+namespace dbcsr_amd {
+
+// 16 bytes of elements: what a lane moves per access where the addresses allow
+template <typename T>
+struct alignas(16) Pack16 {
+  static constexpr int V = 16 / (int)sizeof(T);
+  T v[V];
+};
+
+// ... the same 16 bytes at an address that is only element-aligned: a source block whose start is not congruent to its destination's modulo 16 bytes
+// (blocks of 23 x 23 doubles start at odd elements half of the time) is still read 16 bytes per lane, as one unaligned access or two halves
+template <typename T>
+struct alignas(alignof(T) < 16 ? alignof(T) : 16) Pack16U {
+  T v[Pack16<T>::V];
+};
+
+// bits of `mode`: the scalar is exactly 1 and the operand is taken as it is (bit-identical, NaN and -0 included)
+constexpr int kAlphaIsOne = 1, kBetaIsOne = 2;
+
+template <typename T>
+__device__ __forceinline__ T scaled_by(T x, T s, bool is_one) { return is_one ? x : s * x; }
+
+template <typename T>
+__device__ __forceinline__ T axpby(T a, T b, T alpha, T beta, int mode) {
+  return scaled_by(a, alpha, mode & kAlphaIsOne) + scaled_by(b, beta, mode & kBetaIsOne);
+}
+
+// |x|^2 and the parts of x in double (fp32 data converted first: its products are exact in double)
+__device__ __forceinline__ double abs2_of(double x) { return x * x; }
+__device__ __forceinline__ double abs2_of(float x) { return (double)x * (double)x; }
+__device__ __forceinline__ double abs2_of(z64 x) { return x.re * x.re + x.im * x.im; }
+__device__ __forceinline__ double re_of(double x) { return x; }
+__device__ __forceinline__ double re_of(float x) { return (double)x; }
+__device__ __forceinline__ double re_of(z64 x) { return x.re; }
+__device__ __forceinline__ double im_of(double) { return 0.0; }
+__device__ __forceinline__ double im_of(float) { return 0.0; }
+__device__ __forceinline__ double im_of(z64 x) { return x.im; }
+
+// elements in front of the first 16-byte boundary of a block that starts at element `off` of a 16-byte aligned area
+template <typename T>
+__device__ __forceinline__ int head_of(int64_t off) {
+  constexpr int V = Pack16<T>::V;
+  return (int)((V - (off & (V - 1))) & (V - 1));
+}
+
+// ---- same pattern? ---------------------------------------------------------------------------------------------------
+// S waves per block row of A (both matrices have nblks blocks: the host checked).  flags: bit 0 row_p or col_i differ, bit 1 blk_p differs,
+// bit 2 A is not packed (blk_p is not the running sum of the block sizes).  *nze_out: end of A's last block = its element count when packed.
+__global__ void __launch_bounds__(256) algebra_compare(const int* __restrict__ a_row_p, const int* __restrict__ a_col_i, const int64_t* __restrict__ a_blk_p,
+                                                       const int* __restrict__ b_row_p, const int* __restrict__ b_col_i, const int64_t* __restrict__ b_blk_p,
+                                                       const int* __restrict__ rs, const int* __restrict__ cs, int nbr, int S, int64_t nblks,
+                                                       int* __restrict__ flags, int64_t* __restrict__ nze_out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wv = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int row = (int)(wv / S), sub = (int)(wv % S);
+  if (row >= nbr) return;
+  const int b0 = a_row_p[row], b1 = a_row_p[row + 1];
+  int bad = (b0 != b_row_p[row] || b1 != b_row_p[row + 1]) ? 1 : 0;
+  if (b0 < 0 || b1 > nblks || b1 < b0) bad |= 1;   // (an index that does not belong to these arrays: never read outside them)
+  if (!bad) {
+    const int m = rs[row];
+    for (int b = b0 + sub * 64 + lane; b < b1; b += S * 64) {
+      const int c = a_col_i[b];
+      const int64_t p = a_blk_p[b], end = p + (int64_t)m * cs[c];
+      if (c != b_col_i[b]) bad |= 1;
+      if (p != b_blk_p[b]) bad |= 2;
+      if (b == 0 && p != 0) bad |= 4;
+      if (b + 1 < nblks) {
+        if (a_blk_p[b + 1] != end) bad |= 4;
+      } else {
+        *nze_out = end;
+      }
+    }
+  }
+  if (bad) atomicOr(flags, bad);
+}
+
+// ---- union pattern ----------------------------------------------------------------------------------------------------
+// thread per (row, word): the union bitmap (b_bm == nullptr: A's pattern alone, the add with beta == 0)
+__global__ void __launch_bounds__(256) algebra_union(const uint32_t* __restrict__ a_bm, const uint32_t* __restrict__ b_bm, int64_t nwords,
+                                                     uint32_t* __restrict__ c_bm) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < nwords) c_bm[t] = a_bm[t] | (b_bm ? b_bm[t] : 0u);
+}
+
+// thread per (row, word), in the manner of emit_index: the result's col_i / blk_p and, per result block, the offsets of its sources in A's and B's data
+// areas (src[2 cb], src[2 cb + 1]; -1: the operand has no such block)
+__global__ void __launch_bounds__(256)
+algebra_emit(const int* __restrict__ a_row_p, const int64_t* __restrict__ a_blk_p, const uint32_t* __restrict__ a_bm, const int* __restrict__ a_pre,
+             const int* __restrict__ b_row_p, const int64_t* __restrict__ b_blk_p, const uint32_t* __restrict__ b_bm, const int* __restrict__ b_pre,
+             const uint32_t* __restrict__ c_bm, const int* __restrict__ c_pre, const int* __restrict__ c_row_p, const int64_t* __restrict__ c_blk_p_ws,
+             int nbr, int W, int* __restrict__ c_col_i, int64_t* __restrict__ c_blk_p, int64_t* __restrict__ src) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (int64_t)nbr * W) return;
+  const int i = (int)(t / W), w = (int)(t % W);
+  uint32_t v = c_bm[t];
+  if (!v) return;
+  int cb = c_row_p[i] + c_pre[t];
+  const uint32_t aw = a_bm[t], bw = b_bm ? b_bm[t] : 0u;
+  while (v) {
+    const int bit = __ffs(v) - 1;
+    v &= v - 1;
+    const uint32_t below = (1u << bit) - 1u;
+    c_col_i[cb] = 32 * w + bit;
+    c_blk_p[cb] = c_blk_p_ws[cb];
+    src[2 * (size_t)cb] = ((aw >> bit) & 1u) ? a_blk_p[a_row_p[i] + a_pre[t] + __popc(aw & below)] : -1;
+    src[2 * (size_t)cb + 1] = ((bw >> bit) & 1u) ? b_blk_p[b_row_p[i] + b_pre[t] + __popc(bw & below)] : -1;
+    ++cb;
+  }
+}
+
+// ---- numeric add ------------------------------------------------------------------------------------------------------
+// dst block = alpha * a block + beta * b block, by block row with S waves per row (wave s takes the result blocks s mod S), lanes over the elements.  A block
+// present in one operand only is alpha * a or beta * b; a scalar that is exactly 1 multiplies nothing.  16-byte accesses when dst's area is 16-byte aligned
+// (vec_ok): the stores are aligned -- the elements in front of dst's first boundary and behind its last whole 16 bytes go one by one --, the loads take the
+// same elements from wherever the source blocks start (Pack16U).  dst aliases neither operand (the host refuses it).
+template <typename T>
+__global__ void __launch_bounds__(256)
+algebra_add_blocks(const int* __restrict__ row_p, const int* __restrict__ col_i, const int64_t* __restrict__ blk_p, const int64_t* __restrict__ src,
+                   const int* __restrict__ rs, const int* __restrict__ cs, int nbr, int S, const T* __restrict__ a_data, const T* __restrict__ b_data,
+                   T* __restrict__ d_data, T alpha, T beta, int mode, int vec_ok) {
+  constexpr int V = Pack16<T>::V;
+  const int lane = threadIdx.x & 63;
+  const int64_t wv = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int row = (int)(wv / S), sub = (int)(wv % S);
+  if (row >= nbr) return;
+  const int m = rs[row];
+  for (int t = row_p[row] + sub; t < row_p[row + 1]; t += S) {
+    const int ne = m * cs[col_i[t]];
+    const int64_t ao = src[2 * (size_t)t], bo = src[2 * (size_t)t + 1], dof = blk_p[t];
+    const T* a = a_data + (ao >= 0 ? ao : 0);
+    const T* b = b_data + (bo >= 0 ? bo : 0);
+    T* d = d_data + dof;
+    const int have = (ao >= 0 ? 1 : 0) | (bo >= 0 ? 2 : 0);   // (wave-uniform)
+    auto one = [&](int e) {
+      if (have == 3) d[e] = axpby(a[e], b[e], alpha, beta, mode);
+      else if (have == 1) d[e] = scaled_by(a[e], alpha, mode & kAlphaIsOne);
+      else d[e] = scaled_by(b[e], beta, mode & kBetaIsOne);
+    };
+    if (V == 1 || !vec_ok) {
+      for (int e = lane; e < ne; e += 64) one(e);
+      continue;
+    }
+    const int h = head_of<T>(dof), head = h < ne ? h : ne, nv = (ne - head) / V;
+    if (lane < head) one(lane);
+    const Pack16U<T>* av = reinterpret_cast<const Pack16U<T>*>(a + head);
+    const Pack16U<T>* bv = reinterpret_cast<const Pack16U<T>*>(b + head);
+    Pack16<T>* dv = reinterpret_cast<Pack16<T>*>(d + head);
+    for (int q = lane; q < nv; q += 64) {
+      Pack16<T> r;
+      if (have == 3) {
+        const Pack16U<T> x = av[q], y = bv[q];
+#pragma unroll
+        for (int u = 0; u < V; ++u) r.v[u] = axpby(x.v[u], y.v[u], alpha, beta, mode);
+      } else if (have == 1) {
+        const Pack16U<T> x = av[q];
+#pragma unroll
+        for (int u = 0; u < V; ++u) r.v[u] = scaled_by(x.v[u], alpha, mode & kAlphaIsOne);
+      } else {
+        const Pack16U<T> y = bv[q];
+#pragma unroll
+        for (int u = 0; u < V; ++u) r.v[u] = scaled_by(y.v[u], beta, mode & kBetaIsOne);
+      }
+      dv[q] = r;
+    }
+    const int done = head + nv * V;
+    if (done + lane < ne) one(done + lane);
+  }
+}
+
+// Same pattern, same block offsets, A packed: one flat pass over the n elements of the data areas, dst[i] = alpha * a[i] + beta * b[i].  dst may be a (in
+// place: a lane loads its elements before it stores them, and nobody else touches them).  One 16-byte access per operand and lane, one workgroup per 4 KiB
+// of each area and no loop: on 8.6 GB per area (a += beta * b, float64) this form ran 4.39 ... 4.50 ms where grid-stride loops over 2048 workgroups with 1 ... 8
+// accesses in flight per lane ran 4.6 ... 5.4 ms and torch.add 4.6 ms (tools/ubench/ubench_flat_add.hip, profiles/matrix_ops.txt).  The last n mod V elements
+// go one by one.
+template <typename T>
+__global__ void __launch_bounds__(256) algebra_add_flat(const T* a, const T* b, T* dst, int64_t n, T alpha, T beta, int mode, int vec_ok) {
+  constexpr int V = Pack16<T>::V;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (!vec_ok) {
+    if (i < n) dst[i] = axpby(a[i], b[i], alpha, beta, mode);
+    return;
+  }
+  const int64_t nv = n / V;
+  if (i < nv) {
+    const Pack16<T> x = reinterpret_cast<const Pack16<T>*>(a)[i], y = reinterpret_cast<const Pack16<T>*>(b)[i];
+    Pack16<T> r;
+#pragma unroll
+    for (int k = 0; k < V; ++k) r.v[k] = axpby(x.v[k], y.v[k], alpha, beta, mode);
+    reinterpret_cast<Pack16<T>*>(dst)[i] = r;
+  } else {
+    const int64_t e = nv * V + (i - nv);
+    if (e < n) dst[e] = axpby(a[e], b[e], alpha, beta, mode);
+  }
+}
+
+// ---- the diagonal (dbcsr_add_on_diag) -----------------------------------------------------------------------------------
+// position of the diagonal block of block row `row` in the index, or -1 (every lane gets the answer; any column order)
+__device__ __forceinline__ int find_diag_block(const int* __restrict__ row_p, const int* __restrict__ col_i, int row, int lane) {
+  int found = -1;
+  for (int base = row_p[row]; base < row_p[row + 1] && found < 0; base += 64) {
+    const int b = base + lane;
+    const unsigned long long hit = __ballot(b < row_p[row + 1] && col_i[b] == row);
+    if (hit) found = base + (__ffsll((long long)hit) - 1);
+  }
+  return found;
+}
+
+// one wavefront per block row: need[row] = 1 and blk_nze[row] = m * m when the row has no diagonal block, 0 otherwise
+__global__ void __launch_bounds__(256) diag_missing(const int* __restrict__ row_p, const int* __restrict__ col_i, const int* __restrict__ rs, int nbr,
+                                                    int* __restrict__ need, int* __restrict__ blk_nze) {
+  const int lane = threadIdx.x & 63;
+  const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (row >= nbr) return;
+  const int at = find_diag_block(row_p, col_i, row, lane);
+  if (lane == 0) {
+    need[row] = at < 0 ? 1 : 0;
+    blk_nze[row] = at < 0 ? rs[row] * rs[row] : 0;
+  }
+}
+
+// thread per block row: the index entries of the missing diagonal blocks (d_row_p is the scan of need[], off[] the scan of blk_nze[])
+__global__ void __launch_bounds__(256) diag_emit(const int* __restrict__ need, const int* __restrict__ d_row_p, const int64_t* __restrict__ off, int nbr,
+                                                 int* __restrict__ d_col_i, int64_t* __restrict__ d_blk_p) {
+  const int row = blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= nbr || !need[row]) return;
+  d_col_i[d_row_p[row]] = row;
+  d_blk_p[d_row_p[row]] = off[row];
+}
+
+// one wavefront per block row of a matrix of diagonal blocks: block = alpha * identity
+template <typename T>
+__global__ void __launch_bounds__(256) diag_fill(const int* __restrict__ row_p, const int* __restrict__ col_i, const int64_t* __restrict__ blk_p,
+                                                 const int* __restrict__ rs, int nbr, T alpha, T* __restrict__ data) {
+  const int lane = threadIdx.x & 63;
+  const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (row >= nbr) return;
+  const int m = rs[row];
+  for (int b = row_p[row]; b < row_p[row + 1]; ++b) {
+    if (col_i[b] != row) continue;   // (not a diagonal block: not this kernel's)
+    T* d = data + blk_p[b];
+    for (int e = lane; e < m * m; e += 64) d[e] = (e % m == e / m) ? alpha : T(0);
+  }
+}
+
+// one wavefront per block row, in place: alpha is added to the diagonal elements of the diagonal block the row has (nothing else is written)
+template <typename T>
+__global__ void __launch_bounds__(256) diag_shift(const int* __restrict__ row_p, const int* __restrict__ col_i, const int64_t* __restrict__ blk_p,
+                                                  const int* __restrict__ rs, const int* __restrict__ cs, int nbr, T alpha, T* __restrict__ data) {
+  const int lane = threadIdx.x & 63;
+  const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (row >= nbr) return;
+  const int at = find_diag_block(row_p, col_i, row, lane);
+  if (at < 0) return;
+  const int m = rs[row];
+  if (cs[row] != m) return;   // (not a square block: the caller's sizes are not those of a square matrix; never write outside the block)
+  T* d = data + blk_p[at];
+  for (int e = lane; e < m; e += 64) d[(size_t)e * (m + 1)] = d[(size_t)e * (m + 1)] + alpha;
+}
+
+// ---- reductions ---------------------------------------------------------------------------------------------------------
+// Each writes one pair of doubles per wave (partials[2 wave], partials[2 wave + 1]); checksum_final sums the pairs in a fixed order.
+
+// trace: one wavefront per block row, the diagonal elements of its diagonal block (real part, imaginary part)
+template <typename T>
+__global__ void __launch_bounds__(256) algebra_trace(const int* __restrict__ row_p, const int* __restrict__ col_i, const int64_t* __restrict__ blk_p,
+                                                     const T* __restrict__ data, const int* __restrict__ rs, const int* __restrict__ cs, int nbr,
+                                                     double* __restrict__ partials) {
+  const int lane = threadIdx.x & 63;
+  const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (row >= nbr) return;
+  double sr = 0.0, si = 0.0;
+  const int at = find_diag_block(row_p, col_i, row, lane);
+  if (at >= 0) {
+    const int m = rs[row], n = cs[row], k = m < n ? m : n;
+    const T* d = data + blk_p[at];
+    for (int e = lane; e < k; e += 64) {
+      const T x = d[(size_t)e * (m + 1)];
+      sr += re_of(x);
+      si += im_of(x);
+    }
+  }
+  sr = wave_sum(sr);
+  si = wave_sum(si);
+  if (lane == 0) {
+    partials[2 * (size_t)row] = sr;
+    partials[2 * (size_t)row + 1] = si;
+  }
+}
+
+// squared Frobenius norm: S waves per block row; with `symmetric` a block off the diagonal counts twice (it stands for its twin too)
+template <typename T>
+__global__ void __launch_bounds__(256) algebra_norm2(const int* __restrict__ row_p, const int* __restrict__ col_i, const int64_t* __restrict__ blk_p,
+                                                     const T* __restrict__ data, const int* __restrict__ rs, const int* __restrict__ cs, int nbr, int S,
+                                                     int symmetric, int vec_ok, double* __restrict__ partials) {
+  constexpr int V = Pack16<T>::V;
+  const int lane = threadIdx.x & 63;
+  const int64_t wv = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int row = (int)(wv / S), sub = (int)(wv % S);
+  if (row >= nbr) return;
+  const int m = rs[row];
+  double acc = 0.0;
+  for (int b = row_p[row] + sub; b < row_p[row + 1]; b += S) {
+    const int c = col_i[b], ne = m * cs[c];
+    const int64_t off = blk_p[b];
+    const T* d = data + off;
+    double s = 0.0;
+    if (V > 1 && vec_ok) {
+      const int h = head_of<T>(off), head = h < ne ? h : ne, nv = (ne - head) / V, done = head + nv * V;
+      if (lane < head) s += abs2_of(d[lane]);
+      const Pack16<T>* dv = reinterpret_cast<const Pack16<T>*>(d + head);
+      for (int q = lane; q < nv; q += 64) {
+        const Pack16<T> x = dv[q];
+#pragma unroll
+        for (int u = 0; u < V; ++u) s += abs2_of(x.v[u]);
+      }
+      if (done + lane < ne) s += abs2_of(d[done + lane]);
+    } else {
+      for (int e = lane; e < ne; e += 64) s += abs2_of(d[e]);
+    }
+    acc += (symmetric && c != row) ? 2.0 * s : s;
+  }
+  acc = wave_sum(acc);
+  if (lane == 0) {
+    partials[2 * (size_t)wv] = acc;
+    partials[2 * (size_t)wv + 1] = 0.0;
+  }
+}
+
+// dot (real data): sum a_ij b_ij over the blocks both matrices store.  S waves per block row of A; B's block (row, c) is found by a binary search of B's
+// row (ascending columns, see the head of this file): no work area, nothing a saved plan depends on is touched.
+template <typename T>
+__global__ void __launch_bounds__(256)
+algebra_dot(const int* __restrict__ a_row_p, const int* __restrict__ a_col_i, const int64_t* __restrict__ a_blk_p, const T* __restrict__ a_data,
+            const int* __restrict__ b_row_p, const int* __restrict__ b_col_i, const int64_t* __restrict__ b_blk_p, const T* __restrict__ b_data,
+            const int* __restrict__ rs, const int* __restrict__ cs, int nbr, int S, int symmetric, int vec_ok, double* __restrict__ partials) {
+  constexpr int V = Pack16<T>::V;
+  const int lane = threadIdx.x & 63;
+  const int64_t wv = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int row = (int)(wv / S), sub = (int)(wv % S);
+  if (row >= nbr) return;
+  const int m = rs[row];
+  const int q0 = b_row_p[row], q1 = b_row_p[row + 1];
+  double acc = 0.0;
+  for (int b = a_row_p[row] + sub; b < a_row_p[row + 1]; b += S) {
+    const int c = a_col_i[b];
+    int lo = q0, hi = q1;   // first position of B's row with a column >= c
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (b_col_i[mid] < c) lo = mid + 1; else hi = mid;
+    }
+    if (lo >= q1 || b_col_i[lo] != c) continue;   // (wave-uniform)
+    const int ne = m * cs[c];
+    const int64_t ao = a_blk_p[b], bo = b_blk_p[lo];
+    const T* x = a_data + ao;
+    const T* y = b_data + bo;
+    double s = 0.0;
+    const int h = head_of<T>(ao);
+    if (V > 1 && vec_ok) {   // (aligned on A's block; B's is read from wherever it starts)
+      const int head = h < ne ? h : ne, nv = (ne - head) / V, done = head + nv * V;
+      if (lane < head) s += (double)x[lane] * (double)y[lane];
+      const Pack16<T>* xv = reinterpret_cast<const Pack16<T>*>(x + head);
+      const Pack16U<T>* yv = reinterpret_cast<const Pack16U<T>*>(y + head);
+      for (int q = lane; q < nv; q += 64) {
+        const Pack16<T> p = xv[q];
+        const Pack16U<T> r = yv[q];
+#pragma unroll
+        for (int u = 0; u < V; ++u) s += (double)p.v[u] * (double)r.v[u];
+      }
+      if (done + lane < ne) s += (double)x[done + lane] * (double)y[done + lane];
+    } else {
+      for (int e = lane; e < ne; e += 64) s += (double)x[e] * (double)y[e];
+    }
+    acc += (symmetric && c != row) ? 2.0 * s : s;
+  }
+  acc = wave_sum(acc);
+  if (lane == 0) {
+    partials[2 * (size_t)wv] = acc;
+    partials[2 * (size_t)wv + 1] = 0.0;
+  }
+}
+
+}  // namespace dbcsr_amd
+#endif

@@ -23,7 +23,8 @@
 //   mm_numeric_f32_lds                                     fp32, any sizes up to 32
 //   mm_numeric_f64 / mm_numeric_f32                        blocks above 32 (32 x 32 tiles, fragments from global memory)
 //   mm_numeric_z64<MA,NC>                                  complex_8, any sizes: two accumulator sets, operands in slabs of 8 inner indices (mm_numeric_z64.h)
-// Around them: transpose, checksum, synthetic fill, norm filter, crop / window scale (submatrix limits).
+// Around them: transpose, checksum, synthetic fill, norm filter, crop / window scale (submatrix limits), and the algebra between multiplies
+// (mm_algebra.h: add, add_on_diag, trace, dot, Frobenius norm).
 //
 // Files of this translation unit (included below, inside namespace dbcsr_amd unless they open it themselves):
 //   mm_choose.h          WHICH kernel runs: SizeFacts / Switches / LabSwitches -> NumericChoice, the instance lists and their predicates (plain C++, no HIP)
@@ -34,6 +35,7 @@
 //   mm_engine_plan.h     plan reuse
 //   mm_engine_lab.h      lab build: hosts of the experimental dataflows and their family switch
 //   mm_engine_ops.h      init_c, crop, filter, checksum, fill, transpose, twin moves, statistics
+//   mm_engine_algebra.h  add (count / apply), add_on_diag pieces, trace, dot, norm (kernels: mm_algebra.h)
 // This file: create / destroy, the symbolic phase, and the numeric phase as a sequence -- product lists, choice, set-up, launch, plan bookkeeping.
 #include <hip/hip_runtime.h>
 
@@ -60,6 +62,7 @@
 #include "mm_numeric_f32.h"
 #include "mm_numeric_z64.h"   // complex_8: one family for every block size
 #include "mm_aux.h"
+#include "mm_algebra.h"   // add, add_on_diag, trace, dot, norm: the operations between multiplies
 // The library comes in two builds (Makefile): the SHIPPING one holds what a multiply can run by itself -- the kernels listed above, their
 // symbolic phases, plan reuse -- and the LAB one (-DDBCSR_AMD_EXPERIMENTS, libdbcsr_acc_amd_lab.so) adds every dataflow and variant that
 // was built, made parity-green and measured but does not win: the LDS-DMA ring kernels (mm_dma.h), XCD-wide C tiles (mm_tile.*), CU-wide
@@ -596,6 +599,7 @@ int dbcsr_amd_mm_numeric_z(void* handle, const double alpha[2], const dbcsr_amd_
 }
 
 #include "mm_engine_ops.h"   // init_c, crop, filter, checksum, fill, transpose, twin moves, statistics
+#include "mm_engine_algebra.h"   // add, add_on_diag, trace, dot, norm
 
 }  // extern "C"
 

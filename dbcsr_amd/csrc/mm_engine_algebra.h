@@ -1,0 +1,314 @@
+// mm_engine_algebra.h -- part of mm_engine.hip (included inside extern "C", after mm_engine_ops.h): the C-ABI operations between multiplies --
+// dbcsr_amd_bcsr_add_count / _add_apply, the pieces of dbcsr_add_on_diag (dbcsr_amd_bcsr_diag_count / _diag_fill / _diag_shift), dbcsr_amd_bcsr_trace,
+// _dot, _norm2.  Kernels: mm_algebra.h.  The reductions, the diagonal pieces and the same-pattern add use buffers of their own (Engine::alg_*) and the
+// scan's scratch, which no saved plan depends on (the checksum uses it the same way): they do NOT invalidate the plan.  The union add borrows the
+// symbolic phase's bitmaps and prefix arrays and invalidates it, as filter and crop do.
+#ifndef DBCSR_AMD_MM_ENGINE_ALGEBRA_H
+#define DBCSR_AMD_MM_ENGINE_ALGEBRA_H
+
+extern "C++" {
+template <typename T> static inline T algebra_scalar(const double s[2]);
+template <> inline double algebra_scalar<double>(const double s[2]) { return s[0]; }
+template <> inline float algebra_scalar<float>(const double s[2]) { return (float)s[0]; }   // (the imaginary part of a scalar is ignored for real data)
+template <> inline z64 algebra_scalar<z64>(const double s[2]) { return z64(s[0], s[1]); }
+
+static inline bool algebra_is_one(libsmm_acc_data_t datatype, const double s[2]) { return s[0] == 1.0 && (datatype != dbcsr_type_complex_8 || s[1] == 0.0); }
+static inline int aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0 ? 1 : 0; }
+static inline bool algebra_type(libsmm_acc_data_t datatype) {
+  return datatype == dbcsr_type_real_8 || datatype == dbcsr_type_real_4 || datatype == dbcsr_type_complex_8;
+}
+
+// waves per block row of the per-block add: about four result blocks per wave (config 2's shape at 50 % overlap: 3.35 ms, against 3.52 ms with row_split's
+// 65536 waves; the reductions keep row_split -- every wave they add is a partial more for the one workgroup that sums them)
+static inline int algebra_split(int64_t nbr, int64_t nblks) {
+  if (nbr <= 0) return 1;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(nblks / nbr / 4, 1024));
+}
+
+template <typename T>
+static void add_flat_launch(hipStream_t st, const dbcsr_amd_bcsr* a, const dbcsr_amd_bcsr* b, dbcsr_amd_bcsr* dst, int64_t n, const double alpha[2],
+                            const double beta[2], int mode) {
+  const int vec_ok = aligned16(a->data) & aligned16(b->data) & aligned16(dst->data);
+  const int64_t V = Pack16<T>::V, lanes = vec_ok ? n / V + n % V : n;   // one 16-byte access per lane, the last n mod V elements one lane each
+  hipLaunchKernelGGL((algebra_add_flat<T>), grid_for(lanes), dim3(256), 0, st, static_cast<const T*>(a->data), static_cast<const T*>(b->data),
+                     static_cast<T*>(dst->data), n, algebra_scalar<T>(alpha), algebra_scalar<T>(beta), mode, vec_ok);
+}
+
+template <typename T>
+static void add_blocks_launch(Engine* E, hipStream_t st, const dbcsr_amd_bcsr* a, const dbcsr_amd_bcsr* b, dbcsr_amd_bcsr* dst, const double alpha[2],
+                              const double beta[2], int mode) {
+  const int nbr = dst->nblkrows;
+  const int S = algebra_split(nbr, E->add_nblks);
+  const int vec_ok = aligned16(dst->data);   // (the sources are read from wherever their blocks start)
+  hipLaunchKernelGGL((algebra_add_blocks<T>), grid_for((int64_t)nbr * S * 64), dim3(256), 0, st, dst->row_p, dst->col_i, dst->blk_p, E->prod_start.p,
+                     dst->row_blk_size, dst->col_blk_size, nbr, S, static_cast<const T*>(a->data), static_cast<const T*>(b->data),
+                     static_cast<T*>(dst->data), algebra_scalar<T>(alpha), algebra_scalar<T>(beta), mode, vec_ok);
+}
+
+template <typename T>
+static void diag_launch(hipStream_t st, bool fill, const dbcsr_amd_bcsr* m, const double alpha[2]) {
+  if (fill)
+    hipLaunchKernelGGL((diag_fill<T>), grid_for((int64_t)m->nblkrows * 64), dim3(256), 0, st, m->row_p, m->col_i, m->blk_p, m->row_blk_size, m->nblkrows,
+                       algebra_scalar<T>(alpha), static_cast<T*>(m->data));
+  else
+    hipLaunchKernelGGL((diag_shift<T>), grid_for((int64_t)m->nblkrows * 64), dim3(256), 0, st, m->row_p, m->col_i, m->blk_p, m->row_blk_size, m->col_blk_size, m->nblkrows,
+                       algebra_scalar<T>(alpha), static_cast<T*>(m->data));
+}
+
+// what: 0 trace, 1 norm^2; returns the number of partial pairs written to E->alg_sums
+template <typename T>
+static int64_t reduce_launch(Engine* E, hipStream_t st, int what, const dbcsr_amd_bcsr* a, int symmetric) {
+  const int nbr = a->nblkrows;
+  const int S = what == 0 ? 1 : row_split(nbr, a->nblks);
+  const int64_t nw = (int64_t)nbr * S;
+  if (E->alg_sums.ensure(2 * (size_t)nw + 2)) return -1;
+  if (what == 0)
+    hipLaunchKernelGGL((algebra_trace<T>), grid_for(nw * 64), dim3(256), 0, st, a->row_p, a->col_i, a->blk_p, static_cast<const T*>(a->data),
+                       a->row_blk_size, a->col_blk_size, nbr, E->alg_sums.p);
+  else
+    hipLaunchKernelGGL((algebra_norm2<T>), grid_for(nw * 64), dim3(256), 0, st, a->row_p, a->col_i, a->blk_p, static_cast<const T*>(a->data),
+                       a->row_blk_size, a->col_blk_size, nbr, S, symmetric, aligned16(a->data), E->alg_sums.p);
+  return nw;
+}
+
+template <typename T>
+static int64_t dot_launch(Engine* E, hipStream_t st, const dbcsr_amd_bcsr* a, const dbcsr_amd_bcsr* b, int symmetric) {
+  const int nbr = a->nblkrows;
+  const int S = row_split(nbr, a->nblks);
+  const int64_t nw = (int64_t)nbr * S;
+  if (E->alg_sums.ensure(2 * (size_t)nw + 2)) return -1;
+  hipLaunchKernelGGL((algebra_dot<T>), grid_for(nw * 64), dim3(256), 0, st, a->row_p, a->col_i, a->blk_p, static_cast<const T*>(a->data), b->row_p,
+                     b->col_i, b->blk_p, static_cast<const T*>(b->data), a->row_blk_size, a->col_blk_size, nbr, S, symmetric,
+                     aligned16(a->data), E->alg_sums.p);
+  return nw;
+}
+
+// the partial pairs summed in a fixed order by one workgroup, the two sums brought to the host (synchronises)
+static int reduce_finish(Engine* E, hipStream_t st, int64_t nw, double out2[2], const char* what) {
+  if (nw < 0) return -1;
+  hipLaunchKernelGGL(checksum_final, dim3(1), dim3(256), 0, st, E->alg_sums.p, (int)nw, E->alg_sums.p + 2 * (size_t)nw);
+  ACC_CHECK(hipMemcpyAsync(E->host_scalars + 4, E->alg_sums.p + 2 * (size_t)nw, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  ACC_CHECK(hipStreamSynchronize(st));
+  memcpy(out2, E->host_scalars + 4, 2 * sizeof(double));
+  return check(hipGetLastError(), what, __FILE__, __LINE__);
+}
+}  // extern "C++"
+
+int dbcsr_amd_bcsr_add_count(void* handle, const dbcsr_amd_bcsr* a, const dbcsr_amd_bcsr* b, int beta_is_zero, int32_t* dst_row_p, int64_t* nblks,
+                             int64_t* nze, int* same_pattern, void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E || !a || !b || !dst_row_p || !nblks || !nze || !same_pattern) return -1;
+  if (a->nblkrows != b->nblkrows || a->nblkcols != b->nblkcols) return -1;
+  hipStream_t st = stream_of(stream);
+  const int nbr = a->nblkrows, nbc = a->nblkcols;
+  const int64_t na = a->nblks, nb = beta_is_zero ? 0 : b->nblks;
+  E->add_mode = 0;
+  E->add_beta_zero = beta_is_zero ? 1 : 0;
+  E->add_nblks_a = a->nblks, E->add_nblks_b = b->nblks;
+  *nblks = *nze = 0;
+  *same_pattern = 0;
+  if (E->alg_i32.ensure(4) || E->alg_i64.ensure(8)) return -1;
+  // 1. the same pattern at the same offsets, A packed?  (one small kernel, one flag; a saved plan is not touched)
+  if (!beta_is_zero && na == nb) {
+    int flags = 0;
+    int64_t packed_nze = 0;
+    if (na > 0 && nbr > 0) {
+      ACC_CHECK(hipMemsetAsync(E->alg_i32.p, 0, sizeof(int), st));
+      ACC_CHECK(hipMemsetAsync(E->alg_i64.p, 0, sizeof(int64_t), st));
+      const int S = std::max(1, row_split(nbr, na / 64));   // (a lane per block: a wave covers 64 of them)
+      hipLaunchKernelGGL(algebra_compare, grid_for((int64_t)nbr * S * 64), dim3(256), 0, st, a->row_p, a->col_i, a->blk_p, b->row_p, b->col_i, b->blk_p,
+                         a->row_blk_size, a->col_blk_size, nbr, S, na, E->alg_i32.p, E->alg_i64.p);
+      ACC_CHECK(hipMemcpyAsync(E->host_scalars, E->alg_i32.p, sizeof(int), hipMemcpyDeviceToHost, st));
+      ACC_CHECK(hipMemcpyAsync(E->host_scalars + 1, E->alg_i64.p, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+      ACC_CHECK(hipStreamSynchronize(st));
+      flags = *reinterpret_cast<const int*>(E->host_scalars);
+      packed_nze = E->host_scalars[1];
+    }
+    if (flags == 0) {
+      if (dst_row_p != a->row_p) ACC_CHECK(hipMemcpyAsync(dst_row_p, a->row_p, sizeof(int32_t) * ((size_t)nbr + 1), hipMemcpyDeviceToDevice, st));
+      E->add_mode = 1;
+      *nblks = E->add_nblks = na;
+      *nze = E->add_nze = packed_nze;
+      *same_pattern = 1;
+      return check(hipGetLastError(), "dbcsr_amd_bcsr_add_count", __FILE__, __LINE__);
+    }
+  }
+  // 2. the union pattern, in the symbolic phase's work areas
+  plan_invalidate(E);
+  E->valid = false;
+  const int W = (nbc + 31) / 32;
+  const size_t nw = (size_t)nbr * W;
+  const int64_t cap = na + nb;   // (no more blocks than both operands have)
+  if (E->cin_bm.ensure(nw + 1) || E->b_bm.ensure(nw + 1) || E->c_bm.ensure(nw + 1) || E->cin_pre.ensure(nw + 1) || E->b_pre.ensure(nw + 1) ||
+      E->c_pre.ensure(nw + 1) || E->row_nnz.ensure((size_t)nbr + 1) || E->blk_nze.ensure((size_t)cap + 1) || E->c_blk_p_ws.ensure((size_t)cap + 1) ||
+      E->dev_scalars.ensure(16))
+    return -1;
+  int64_t* dsc = reinterpret_cast<int64_t*>(E->dev_scalars.p);
+  ACC_CHECK(hipMemsetAsync(dsc, 0, 16 * sizeof(int64_t), st));
+  if (nw > 0) {
+    ACC_CHECK(hipMemsetAsync(E->cin_bm.p, 0, sizeof(uint32_t) * nw, st));
+    if (na > 0) hipLaunchKernelGGL(bitmap_from_index, grid_for((int64_t)nbr * 64), dim3(256), 0, st, a->row_p, a->col_i, nbr, W, E->cin_bm.p);
+    if (!beta_is_zero) {
+      ACC_CHECK(hipMemsetAsync(E->b_bm.p, 0, sizeof(uint32_t) * nw, st));
+      if (nb > 0) hipLaunchKernelGGL(bitmap_from_index, grid_for((int64_t)nbr * 64), dim3(256), 0, st, b->row_p, b->col_i, nbr, W, E->b_bm.p);
+      hipLaunchKernelGGL(row_prefix, grid_for((int64_t)nbr * 64), dim3(256), 0, st, E->b_bm.p, nbr, W, E->b_pre.p, (int*)nullptr);
+    }
+    hipLaunchKernelGGL(algebra_union, grid_for((int64_t)nw), dim3(256), 0, st, E->cin_bm.p, beta_is_zero ? (const uint32_t*)nullptr : E->b_bm.p,
+                       (int64_t)nw, E->c_bm.p);
+    hipLaunchKernelGGL(row_prefix, grid_for((int64_t)nbr * 64), dim3(256), 0, st, E->cin_bm.p, nbr, W, E->cin_pre.p, (int*)nullptr);
+    hipLaunchKernelGGL(row_prefix, grid_for((int64_t)nbr * 64), dim3(256), 0, st, E->c_bm.p, nbr, W, E->c_pre.p, E->row_nnz.p);
+  } else if (nbr > 0) {
+    ACC_CHECK(hipMemsetAsync(E->row_nnz.p, 0, sizeof(int) * (size_t)nbr, st));
+  }
+  if (exclusive_scan<int32_t>(E, E->row_nnz.p, nbr, dst_row_p, dsc + 0, true, st)) return -1;
+  if (cap > 0 && nw > 0) {
+    ACC_CHECK(hipMemsetAsync(E->blk_nze.p, 0, sizeof(int) * (size_t)cap, st));   // (the scan runs over cap entries: those behind the last block count nothing)
+    hipLaunchKernelGGL(block_sizes_rows, grid_for((int64_t)nw), dim3(256), 0, st, E->c_bm.p, E->c_pre.p, dst_row_p, a->row_blk_size, a->col_blk_size, nbr,
+                       W, E->blk_nze.p);
+    if (exclusive_scan<int64_t>(E, E->blk_nze.p, cap, E->c_blk_p_ws.p, dsc + 1, false, st)) return -1;
+  }
+  ACC_CHECK(hipMemcpyAsync(E->host_scalars, dsc, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  ACC_CHECK(hipStreamSynchronize(st));
+  E->add_mode = 2;
+  *nblks = E->add_nblks = E->host_scalars[0];
+  *nze = E->add_nze = E->host_scalars[1];
+  return check(hipGetLastError(), "dbcsr_amd_bcsr_add_count", __FILE__, __LINE__);
+}
+
+int dbcsr_amd_bcsr_add_apply(void* handle, libsmm_acc_data_t datatype, const double alpha[2], const dbcsr_amd_bcsr* a, const double beta[2],
+                             const dbcsr_amd_bcsr* b, dbcsr_amd_bcsr* dst, void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E || !alpha || !a || !beta || !b || !dst) return -1;
+  if (!algebra_type(datatype)) return -10;
+  const int pending = E->add_mode;
+  E->add_mode = 0;
+  if (!pending || a->nblks != E->add_nblks_a || b->nblks != E->add_nblks_b || a->nblkrows != b->nblkrows || a->nblkcols != b->nblkcols ||
+      dst->nblkrows != a->nblkrows || dst->nblkcols != a->nblkcols)
+    return -1;
+  hipStream_t st = stream_of(stream);
+  const int mode = (algebra_is_one(datatype, alpha) ? kAlphaIsOne : 0) | (algebra_is_one(datatype, beta) ? kBetaIsOne : 0);
+  dst->nblks = E->add_nblks;
+  if (pending == 1) {   // same pattern: one flat pass, in place when dst is a (the index is then not touched at all)
+    if (E->add_nblks == 0) return 0;
+    if (dst->col_i != a->col_i) ACC_CHECK(hipMemcpyAsync(dst->col_i, a->col_i, sizeof(int32_t) * (size_t)a->nblks, hipMemcpyDeviceToDevice, st));
+    if (dst->blk_p != a->blk_p) ACC_CHECK(hipMemcpyAsync(dst->blk_p, a->blk_p, sizeof(int64_t) * (size_t)a->nblks, hipMemcpyDeviceToDevice, st));
+    if (datatype == dbcsr_type_real_8)
+      add_flat_launch<double>(st, a, b, dst, E->add_nze, alpha, beta, mode);
+    else if (datatype == dbcsr_type_real_4)
+      add_flat_launch<float>(st, a, b, dst, E->add_nze, alpha, beta, mode);
+    else
+      add_flat_launch<z64>(st, a, b, dst, E->add_nze, alpha, beta, mode);
+    return check(hipGetLastError(), "dbcsr_amd_bcsr_add_apply", __FILE__, __LINE__);
+  }
+  plan_invalidate(E);  // this call uses the engine's work areas: the next multiply runs its own symbolic phase
+  if (E->add_nblks == 0) return 0;
+  if (dst->data == a->data || (!E->add_beta_zero && dst->data == b->data)) return -1;   // the union add is not done in place
+  const int nbr = a->nblkrows, W = (a->nblkcols + 31) / 32;
+  if (E->prod_start.ensure(2 * (size_t)E->add_nblks + 2)) return -1;
+  hipLaunchKernelGGL(algebra_emit, grid_for((int64_t)nbr * W), dim3(256), 0, st, a->row_p, a->blk_p, E->cin_bm.p, E->cin_pre.p, b->row_p, b->blk_p,
+                     E->add_beta_zero ? (const uint32_t*)nullptr : E->b_bm.p, E->b_pre.p, E->c_bm.p, E->c_pre.p, dst->row_p, E->c_blk_p_ws.p, nbr, W,
+                     dst->col_i, dst->blk_p, E->prod_start.p);
+  if (datatype == dbcsr_type_real_8)
+    add_blocks_launch<double>(E, st, a, b, dst, alpha, beta, mode);
+  else if (datatype == dbcsr_type_real_4)
+    add_blocks_launch<float>(E, st, a, b, dst, alpha, beta, mode);
+  else
+    add_blocks_launch<z64>(E, st, a, b, dst, alpha, beta, mode);
+  return check(hipGetLastError(), "dbcsr_amd_bcsr_add_apply", __FILE__, __LINE__);
+}
+
+int dbcsr_amd_bcsr_diag_count(void* handle, const dbcsr_amd_bcsr* m, int32_t* dst_row_p, int32_t* dst_col_i, int64_t* dst_blk_p, int64_t* nblks,
+                              int64_t* nze, void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E || !m || !dst_row_p || !nblks || !nze || m->nblkrows != m->nblkcols) return -1;
+  hipStream_t st = stream_of(stream);
+  const int nbr = m->nblkrows;
+  *nblks = *nze = 0;
+  if (nbr > 0 && (!dst_col_i || !dst_blk_p)) return -1;
+  if (E->alg_i32.ensure(4 + 2 * (size_t)nbr) || E->alg_i64.ensure(8 + (size_t)nbr + 1)) return -1;
+  int* need = E->alg_i32.p + 4;
+  int* sizes = need + nbr;
+  int64_t* off = E->alg_i64.p + 8;
+  ACC_CHECK(hipMemsetAsync(E->alg_i64.p, 0, 2 * sizeof(int64_t), st));
+  if (nbr > 0)
+    hipLaunchKernelGGL(diag_missing, grid_for((int64_t)nbr * 64), dim3(256), 0, st, m->row_p, m->col_i, m->row_blk_size, nbr, need, sizes);
+  if (exclusive_scan<int32_t>(E, need, nbr, dst_row_p, E->alg_i64.p + 0, true, st)) return -1;
+  if (exclusive_scan<int64_t>(E, sizes, nbr, off, E->alg_i64.p + 1, false, st)) return -1;
+  if (nbr > 0) hipLaunchKernelGGL(diag_emit, grid_for(nbr), dim3(256), 0, st, need, dst_row_p, off, nbr, dst_col_i, dst_blk_p);
+  ACC_CHECK(hipMemcpyAsync(E->host_scalars, E->alg_i64.p, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  ACC_CHECK(hipStreamSynchronize(st));
+  *nblks = E->host_scalars[0];
+  *nze = E->host_scalars[1];
+  return check(hipGetLastError(), "dbcsr_amd_bcsr_diag_count", __FILE__, __LINE__);
+}
+
+static int diag_any(void* handle, libsmm_acc_data_t datatype, bool fill, const double alpha[2], const dbcsr_amd_bcsr* m, void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E || !alpha || !m || m->nblkrows != m->nblkcols) return -1;
+  if (!algebra_type(datatype)) return -10;
+  hipStream_t st = stream_of(stream);
+  if (m->nblkrows == 0 || m->nblks == 0) return 0;
+  if (datatype == dbcsr_type_real_8)
+    diag_launch<double>(st, fill, m, alpha);
+  else if (datatype == dbcsr_type_real_4)
+    diag_launch<float>(st, fill, m, alpha);
+  else
+    diag_launch<z64>(st, fill, m, alpha);
+  return check(hipGetLastError(), fill ? "dbcsr_amd_bcsr_diag_fill" : "dbcsr_amd_bcsr_diag_shift", __FILE__, __LINE__);
+}
+
+int dbcsr_amd_bcsr_diag_fill(void* handle, libsmm_acc_data_t datatype, const double alpha[2], dbcsr_amd_bcsr* dst, void* stream) {
+  return diag_any(handle, datatype, true, alpha, dst, stream);
+}
+
+int dbcsr_amd_bcsr_diag_shift(void* handle, libsmm_acc_data_t datatype, dbcsr_amd_bcsr* m, const double alpha[2], void* stream) {
+  return diag_any(handle, datatype, false, alpha, m, stream);
+}
+
+int dbcsr_amd_bcsr_trace(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, double out[2], void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E || !m || !out || m->nblkrows != m->nblkcols) return -1;
+  if (!algebra_type(datatype)) return -10;
+  hipStream_t st = stream_of(stream);
+  out[0] = out[1] = 0.0;
+  if (m->nblkrows == 0 || m->nblks == 0) return 0;
+  const int64_t nw = datatype == dbcsr_type_real_8   ? reduce_launch<double>(E, st, 0, m, 0)
+                     : datatype == dbcsr_type_real_4 ? reduce_launch<float>(E, st, 0, m, 0)
+                                                     : reduce_launch<z64>(E, st, 0, m, 0);
+  return reduce_finish(E, st, nw, out, "dbcsr_amd_bcsr_trace");
+}
+
+int dbcsr_amd_bcsr_norm2(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, int symmetric, double out[1], void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E || !m || !out) return -1;
+  if (!algebra_type(datatype)) return -10;
+  hipStream_t st = stream_of(stream);
+  out[0] = 0.0;
+  if (m->nblkrows == 0 || m->nblks == 0) return 0;
+  const int sym = symmetric ? 1 : 0;
+  const int64_t nw = datatype == dbcsr_type_real_8   ? reduce_launch<double>(E, st, 1, m, sym)
+                     : datatype == dbcsr_type_real_4 ? reduce_launch<float>(E, st, 1, m, sym)
+                                                     : reduce_launch<z64>(E, st, 1, m, sym);
+  double two[2] = {0.0, 0.0};
+  const int rc = reduce_finish(E, st, nw, two, "dbcsr_amd_bcsr_norm2");
+  out[0] = two[0];
+  return rc;
+}
+
+int dbcsr_amd_bcsr_dot(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* a, const dbcsr_amd_bcsr* b, int symmetric, double out[1],
+                       void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E || !a || !b || !out || a->nblkrows != b->nblkrows || a->nblkcols != b->nblkcols) return -1;
+  if (datatype != dbcsr_type_real_8 && datatype != dbcsr_type_real_4) return -10;   // (complex data: not offered, see the header)
+  hipStream_t st = stream_of(stream);
+  out[0] = 0.0;
+  if (a->nblkrows == 0 || a->nblks == 0 || b->nblks == 0) return 0;
+  const int sym = symmetric ? 1 : 0;
+  const int64_t nw = datatype == dbcsr_type_real_8 ? dot_launch<double>(E, st, a, b, sym) : dot_launch<float>(E, st, a, b, sym);
+  double two[2] = {0.0, 0.0};
+  const int rc = reduce_finish(E, st, nw, two, "dbcsr_amd_bcsr_dot");
+  out[0] = two[0];
+  return rc;
+}
+
+#endif

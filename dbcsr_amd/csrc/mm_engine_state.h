@@ -118,6 +118,15 @@ struct Engine {
   bool crop_pending = false;
   KPassMemo kpass_memo;  // dbcsr_amd_multiply's k-pass decision for the last stamped A operand (mm_api.hip)
 
+  // ---- matrix algebra (mm_engine_algebra.h): buffers of its own, nothing a saved plan depends on.  Only the general (union) add borrows the symbolic
+  // work areas, and invalidates the plan ----
+  DevBuf<double> alg_sums;    // reductions: one pair of doubles per wave, the result behind them
+  DevBuf<int> alg_i32;        // [0] flags of algebra_compare; diag: need[nbr], blk_nze[nbr]
+  DevBuf<int64_t> alg_i64;    // [0 ... 7] scalars; diag: offsets of the missing diagonal blocks
+  int add_mode = 0;           // what the last dbcsr_amd_bcsr_add_count found: 0 nothing pending, 1 same pattern (flat pass), 2 union pattern
+  int add_beta_zero = 0;
+  int64_t add_nblks_a = 0, add_nblks_b = 0, add_nblks = 0, add_nze = 0;
+
   // ---- switches (mm_engine_env.h) ----
   Switches sw;      // the numeric phase's kernel families (mm_choose.h)
   LabSwitches lab;  // lab build only: no state in the shipping build

@@ -39,6 +39,9 @@ MM_SYMBOLS = [
     # complex_8: complex scalars as double[2] = {re, im}
     "dbcsr_amd_mm_numeric_z", "dbcsr_amd_mm_init_c_z", "dbcsr_amd_bcsr_scale_window_z", "dbcsr_amd_bcsr_transpose_conj", "dbcsr_amd_multiply_z",
     "dbcsr_amd_multiply_symmetric_c_z",
+    # matrix algebra between multiplies (dbcsr_amd/operations.py)
+    "dbcsr_amd_bcsr_add_count", "dbcsr_amd_bcsr_add_apply", "dbcsr_amd_bcsr_diag_count", "dbcsr_amd_bcsr_diag_fill", "dbcsr_amd_bcsr_diag_shift",
+    "dbcsr_amd_bcsr_trace", "dbcsr_amd_bcsr_dot", "dbcsr_amd_bcsr_norm2",
 ]
 
 # `kind` of a matrix with symmetry in the C ABI (include/dbcsr_amd_mm.h): bit 0 negates the twin block, bit 1 conjugates it
@@ -184,6 +187,14 @@ def load_library(lab=False):
     L.dbcsr_amd_bcsr_transpose_conj.argtypes = [vp, i32, BP, BP, vp]
     L.dbcsr_amd_multiply_z.argtypes = [vp, C.c_char, C.c_char, Z, BP, BP, Z, BP, C.POINTER(i64), i32, C.c_double, BP, C.POINTER(i64), vp]
     L.dbcsr_amd_multiply_symmetric_c_z.argtypes = [vp, C.c_char, C.c_char, Z, BP, BP, Z, BP, i32, i64, i64, i32, C.c_double, BP, C.POINTER(i64), vp]
+    L.dbcsr_amd_bcsr_add_count.argtypes = [vp, BP, BP, i32, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32), vp]
+    L.dbcsr_amd_bcsr_add_apply.argtypes = [vp, i32, Z, BP, Z, BP, BP, vp]
+    L.dbcsr_amd_bcsr_diag_count.argtypes = [vp, BP, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), vp]
+    L.dbcsr_amd_bcsr_diag_fill.argtypes = [vp, i32, Z, BP, vp]
+    L.dbcsr_amd_bcsr_diag_shift.argtypes = [vp, i32, BP, Z, vp]
+    L.dbcsr_amd_bcsr_trace.argtypes = [vp, i32, BP, Z, vp]
+    L.dbcsr_amd_bcsr_dot.argtypes = [vp, i32, BP, BP, i32, Z, vp]
+    L.dbcsr_amd_bcsr_norm2.argtypes = [vp, i32, BP, i32, Z, vp]
     if lab:   # diagnostics of the experimental dataflows (dbcsr_amd/csrc/mm_lab_api.h): the shipping build does not export them
         L.dbcsr_amd_mm_tile_stats.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
         L.dbcsr_amd_mm_band_stats.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]

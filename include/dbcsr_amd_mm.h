@@ -295,6 +295,53 @@ int dbcsr_amd_mm_trust_plan(void* handle, int on);
 int dbcsr_amd_mm_expect_filter(void* handle, double eps);
 int dbcsr_amd_mm_plan_stats(void* handle, int64_t* reused, int64_t* built);
 
+/* Matrix algebra between multiplies (src/ops/dbcsr_operations.F: dbcsr_add, dbcsr_scale, dbcsr_add_on_diag, dbcsr_trace, dbcsr_dot, dbcsr_frobenius_norm) on
+ * device-resident matrices, for dbcsr_type_real_8, dbcsr_type_real_4 and dbcsr_type_complex_8 (any other type code: -10; the dot: real types only).  Every
+ * operation goes by the index (row_p, col_i, blk_p), never by the extent of a data area: the result of an in-place filter is an operand like any other.
+ * The block columns of every block row must be in ascending order (as in every matrix this library makes): the position of a block inside its row is found
+ * from the number of blocks with a smaller column, the same convention by which the multiply finds a block of C_in.  NULL arguments and matrices whose
+ * nblkrows / nblkcols differ: -1.  Complex scalars are double[2] = {re, im}; the imaginary part is ignored for real data.
+ *
+ * dbcsr_add: A <- alpha*A + beta*B.  The result's pattern is the union of both patterns, blocks packed in index order; a block one operand lacks counts as
+ * zero there (the block is alpha*a or beta*b, and with a scalar that is exactly 1 it is bit-identical to its source); blocks of A stay stored with
+ * alpha == 0.  beta_is_zero: B's pattern is NOT merged -- the result is alpha*A on A's pattern and B is never read.  Matrices with symmetry are added on
+ * their stored triangles as they are (the caller checks that both have the same symmetry).  Two steps, as filter and crop:
+ *   _add_count   writes dst_row_p [nblkrows + 1] (device) and the block / element counts of the result (host; synchronises).  *same_pattern = 1: A and B have
+ *     the same row_p, col_i AND blk_p and A is packed -- compared on the device, with buffers no saved plan depends on.  Otherwise the union pattern is
+ *     formed in the work areas of the symbolic phase: the handle's saved plan is invalidated, as by a filter or a crop.
+ *   _add_apply   fills dst (dst->row_p = that row_p; col_i, blk_p [nblks], data [nze] allocated by the caller).  When _count reported same_pattern, dst may be
+ *     a itself: one flat pass over the data area in place, no index array is written (a multiply with A as operand afterwards still reuses its plan).
+ *     Otherwise a dst whose data area is a's or b's is refused (-1).  One _apply per _count.  Asynchronous on stream.
+ * With alpha == beta == 1 on the same pattern the result is a + b in the data's own precision, bit for bit. */
+int dbcsr_amd_bcsr_add_count(void* handle, const dbcsr_amd_bcsr* a, const dbcsr_amd_bcsr* b, int beta_is_zero, int32_t* dst_row_p, int64_t* nblks,
+  int64_t* nze, int* same_pattern, void* stream);
+int dbcsr_amd_bcsr_add_apply(void* handle, libsmm_acc_data_t datatype, const double alpha[2], const dbcsr_amd_bcsr* a, const double beta[2],
+  const dbcsr_amd_bcsr* b, dbcsr_amd_bcsr* dst, void* stream);
+/* dbcsr_scale of the whole matrix is dbcsr_amd_bcsr_scale_window / _scale_window_z with no bounds (all four negative).
+ *
+ * dbcsr_add_on_diag (square matrix, row_blk_size == col_blk_size): alpha is added to every diagonal element; diagonal blocks the matrix lacks are created.
+ *   _diag_shift  in place: adds alpha to the diagonal elements of the diagonal blocks m HAS; nothing else is written, no index array is touched.
+ *   _diag_count  the index of the block-diagonal matrix of the diagonal blocks m LACKS: dst_row_p [nblkrows + 1], dst_col_i / dst_blk_p [nblkrows] (device,
+ *     the first *nblks entries are written), *nblks and *nze on the host (synchronises).  No saved plan is touched.
+ *   _diag_fill   every diagonal block of dst = alpha * identity.
+ * add_on_diag is _diag_shift, and when blocks are missing the add (alpha = beta = 1) of the matrix made by _diag_count / _diag_fill: old elements off the
+ * diagonal stay bit-identical, new blocks are alpha * I. */
+int dbcsr_amd_bcsr_diag_count(void* handle, const dbcsr_amd_bcsr* m, int32_t* dst_row_p, int32_t* dst_col_i, int64_t* dst_blk_p, int64_t* nblks,
+  int64_t* nze, void* stream);
+int dbcsr_amd_bcsr_diag_fill(void* handle, libsmm_acc_data_t datatype, const double alpha[2], dbcsr_amd_bcsr* dst, void* stream);
+int dbcsr_amd_bcsr_diag_shift(void* handle, libsmm_acc_data_t datatype, dbcsr_amd_bcsr* m, const double alpha[2], void* stream);
+/* Reductions.  Sums are formed in double (fp32 data converted first), one partial per wave, the partials summed in a fixed order by one workgroup: no
+ * floating-point atomics, the same bits on every call.  They use buffers of their own: a saved plan stays.  Each synchronises stream.
+ *   _trace  out = {re, im} of the sum of the diagonal elements of the diagonal blocks present (square block structure; im = 0 for real data).
+ *   _dot    out[0] = sum a_ij * b_ij over the blocks BOTH matrices store = trace(A^T B).  symmetric != 0 (both matrices symmetric, stored triangles): blocks
+ *           off the diagonal count twice.  Real types only, -10 for complex_8: whether the reference conjugates one operand could not be checked against its
+ *           sources, so the complex dot is not offered rather than guessed.
+ *   _norm2  out[0] = sum |x|^2, the SQUARED Frobenius norm.  symmetric != 0 (any of the four symmetries): blocks off the diagonal count twice. */
+int dbcsr_amd_bcsr_trace(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, double out[2], void* stream);
+int dbcsr_amd_bcsr_dot(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* a, const dbcsr_amd_bcsr* b, int symmetric, double out[1],
+  void* stream);
+int dbcsr_amd_bcsr_norm2(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, int symmetric, double out[1], void* stream);
+
 /* Measurement helper (bench.py, roofline.fabric): what the L2 <-> Infinity-Cache fabric of the current device delivers, in TB/s -- a
  * plain streaming read of a 160 MB window by all CUs, and the block gather of the block-product dataflow (4232-byte blocks from
  * pseudo-random places of the window into LDS, whole 128-byte lines counted).  Takes well under a second; synchronises the device. */

@@ -1,0 +1,148 @@
+#!/usr/bin/env python3
+"""Times of the matrix algebra between multiplies (dbcsr_amd/operations.py, kernels of dbcsr_amd/csrc/mm_algebra.h) on matrices of the shape of
+config 2's product (n x n, uniform b x b blocks; BASELINE.json: 32768, 23), next to torch kernels that move the same bytes, in the same process,
+alternating:
+
+    python tools/ops_bench.py --n 32768 --block 23 --alternations 7 --warmup 2 --out profiles/matrix_ops.txt
+
+  flat        dbcsr_add on the same pattern (A <- A + beta B in place): the comparison of the two indices on the device with its synchronisation
+              (flat.count: dbcsr_amd_bcsr_add_count alone) and the flat pass algebra_add_flat; pattern fill --fill-flat
+  torch.add   torch.add(a.data, b.data, alpha=beta, out=a.data) on the two flat data tensors: the same bytes through a kernel that is not ours
+  general     dbcsr_amd_bcsr_add_count + _add_apply at 50 % pattern overlap (A and B of fill --fill-general, half of each one's blocks in the other):
+              bitmaps, union, scans, one synchronisation, index emission, algebra_add_blocks; dst allocated once
+  apply       of that, the part after the count's synchronisation (index emission + algebra_add_blocks), from the difference to a count alone
+  norm        dbcsr_amd_bcsr_norm2 of A (algebra_norm2 + the final sum + one synchronisation)
+  torch.norm  torch.linalg.vector_norm(a.data): the same bytes read
+
+A sample is `--reps` calls back to back between two device events, divided by reps.  Bytes are counted from the shapes: 8 * (elements read + elements
+written) of the data areas, index arrays left out.  Spread = (max - min) / median over the samples."""
+import argparse
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from dbcsr_amd import lib as L  # noqa: E402
+from dbcsr_amd.matrix import DbcsrMatrix, StreamHandle  # noqa: E402
+from dbcsr_amd.multiply import MultiplyEngine  # noqa: E402
+from dbcsr_amd.operations import dbcsr_add  # noqa: E402
+
+
+def matrix_of(mask, b, seed):
+    """uniform b x b blocks on the pattern `mask` (block rows x block columns), packed, uniform(-0.5, 0.5) values made on the device"""
+    nb = mask.shape[0]
+    rows, cols = np.nonzero(mask)
+    row_p = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=nb))]).astype(np.int32)
+    sizes = torch.full((nb,), b, dtype=torch.int32, device="cuda")
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    data = torch.rand(len(rows) * b * b, dtype=torch.float64, device="cuda", generator=g) - 0.5
+    t = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a), dtype=dt).cuda()
+    return DbcsrMatrix(sizes, sizes, t(row_p, torch.int32), t(cols, torch.int32), t(np.arange(len(rows), dtype=np.int64) * b * b, torch.int64), data)
+
+
+def sample(fn, reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=32768)
+    ap.add_argument("--block", type=int, default=23)
+    ap.add_argument("--fill-flat", type=float, default=1.0, help="pattern fill of the same-pattern add and the norm (config 2's product is full)")
+    ap.add_argument("--fill-general", type=float, default=0.5, help="pattern fill of each operand of the general add (at most 2/3)")
+    ap.add_argument("--alternations", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--out", default=None, help="also write the report to this file")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "ops_bench.py measures on the GPU"
+    assert 0 < args.fill_general <= 2.0 / 3
+    b, nb = args.block, args.n // args.block
+    lines = []
+    say = lambda s: (print(s, flush=True), lines.append(s))
+    say("matrix algebra between multiplies, float64, %d x %d block rows / columns of %d x %d blocks (n = %d); %s" % (nb, nb, b, b, args.n, torch.cuda.get_device_name(0)))
+    say("%d alternations after %d warm-up rounds, %d calls per sample; ms per call; GB/s = 8 * (elements read + written) / time" % (args.alternations, args.warmup, args.reps))
+    E, st = MultiplyEngine(), StreamHandle()
+    rng = np.random.default_rng(2)
+    # the same-pattern pair
+    mask = rng.random((nb, nb)) < args.fill_flat
+    A, B = matrix_of(mask, b, 1), matrix_of(mask, b, 2)
+    beta = 1e-3
+    # the general pair: three disjoint random sets of blocks S, SA, SB of equal size; A = S + SA, B = S + SB
+    u = rng.random((nb, nb))
+    q = args.fill_general / 2
+    GA, GB = matrix_of((u < 2 * q), b, 3), matrix_of((u < q) | ((u >= 2 * q) & (u < 3 * q)), b, 4)
+    ga, gb = GA.desc(), GB.desc()
+    row_p = torch.empty(nb + 1, dtype=torch.int32, device="cuda")
+    nblk, nze, same = C.c_int64(), C.c_int64(), C.c_int32()
+    count = lambda: E.L.dbcsr_amd_bcsr_add_count(E.h, C.byref(ga), C.byref(gb), 0, row_p.data_ptr(), C.byref(nblk), C.byref(nze), C.byref(same), st.ptr)
+    assert count() == 0 and same.value == 0
+    D = DbcsrMatrix(GA.row_blk_size, GA.col_blk_size, row_p, torch.empty(nblk.value, dtype=torch.int32, device="cuda"),
+                    torch.empty(nblk.value, dtype=torch.int64, device="cuda"), torch.empty(nze.value, dtype=torch.float64, device="cuda"))
+    gd = D.desc(out=True)
+    one, two = (C.c_double * 2)(1.0, 0.0), (C.c_double * 2)(beta, 0.0)
+    shared = int(np.count_nonzero(u < q))
+    out2 = (C.c_double * 2)()
+    a = A.desc()
+
+    b_ = B.desc()
+    row_p_same = torch.empty(nb + 1, dtype=torch.int32, device="cuda")
+    nblk_s, nze_s, same_s = C.c_int64(), C.c_int64(), C.c_int32()
+    count_same = lambda: E.L.dbcsr_amd_bcsr_add_count(E.h, C.byref(a), C.byref(b_), 0, row_p_same.data_ptr(), C.byref(nblk_s), C.byref(nze_s), C.byref(same_s), st.ptr)
+
+    def general():
+        assert count() == 0
+        assert E.L.dbcsr_amd_bcsr_add_apply(E.h, L.dbcsr_type_real_8, one, C.byref(ga), two, C.byref(gb), C.byref(gd), st.ptr) == 0
+
+    def flat():
+        assert dbcsr_add(A, B, 1.0, beta, engine=E) is True
+
+    run = {
+        "flat": flat,
+        "torch.add": lambda: torch.add(A.data, B.data, alpha=beta, out=A.data),
+        "flat.count": lambda: count_same(),
+        "general": general,
+        "count": lambda: count(),
+        "norm": lambda: E.L.dbcsr_amd_bcsr_norm2(E.h, L.dbcsr_type_real_8, C.byref(a), 0, out2, st.ptr),
+        "torch.norm": lambda: torch.linalg.vector_norm(A.data),
+    }
+    nbytes = {"flat": 24 * A.nze, "torch.add": 24 * A.nze, "flat.count": 0, "general": 8 * (GA.nze + GB.nze + nze.value), "count": 0, "norm": 8 * A.nze, "torch.norm": 8 * A.nze}
+    times = {k: [] for k in run}
+    for step in range(args.warmup + args.alternations):
+        for k in run:
+            t = sample(run[k], args.reps)
+            if step >= args.warmup:
+                times[k].append(t)
+    say("")
+    say("same pattern: %d blocks, %.1f MB per matrix; general: %d and %d blocks (%.1f MB each), %d shared (%.0f %% of each), %d in the union (%.1f MB)"
+        % (A.nblks, 8e-6 * A.nze, GA.nblks, GB.nblks, 8e-6 * GA.nze, shared, 100.0 * shared / max(1, GA.nblks), nblk.value, 8e-6 * nze.value))
+    med = {}
+    for k in run:
+        v = sorted(times[k])
+        med[k] = v[len(v) // 2]
+        rate = ("%8.1f GB/s" % (1e-6 * nbytes[k] / med[k])) if nbytes[k] else "   (no data moved)"
+        say("  %-10s  median %8.4f ms  min %8.4f  max %8.4f  spread %5.1f %%  %s   samples: %s"
+            % (k, med[k], v[0], v[-1], 100 * (v[-1] - v[0]) / med[k], rate, " ".join("%.4f" % x for x in times[k])))
+    flat_ms = med["flat"] - med["flat.count"]
+    say("  flat kernel = flat - flat.count: %.4f ms, %.1f GB/s, %.2f of torch.add's rate" % (flat_ms, 1e-6 * nbytes["flat"] / flat_ms, med["torch.add"] / flat_ms))
+    apply_ms = med["general"] - med["count"]
+    say("  apply = general - count: %.4f ms, %.1f GB/s" % (apply_ms, 1e-6 * nbytes["general"] / apply_ms))
+    flat_rate, torch_rate = nbytes["flat"] / med["flat"], nbytes["torch.add"] / med["torch.add"]
+    say("  flat against torch.add: %.2f of its rate; general (count + apply) against torch.add: %.2f; apply alone: %.2f; norm against torch.norm: %.2f"
+        % (flat_rate / torch_rate, nbytes["general"] / med["general"] / torch_rate, nbytes["general"] / apply_ms / torch_rate, med["torch.norm"] / med["norm"]))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
