@@ -397,5 +397,408 @@ algebra_dot(const int* __restrict__ a_row_p, const int* __restrict__ a_col_i, co
   }
 }
 
+// ---- norms and vectors (dbcsr_norm, dbcsr_gershgorin_norm, dbcsr_maxabs_norm, dbcsr_get_diag / _set_diag, dbcsr_scale_by_vector) --------------------
+// A result or an operand per FULL row or column of the matrix: a kernel must know where an element sits inside its column-major block (element row e % m,
+// element column e / m), and the element offset of its block row / column (roff / coff: exclusive scans of the block sizes, formed on the device).  Sums are
+// carried in double and written once per wave (S partial vectors); algebra_vec_combine adds the partial vectors in a fixed order.  No atomics.
+
+// what == 0: |x|, what == 1: |x|^2, in double (fp32 data converted first; |z| as the root of re^2 + im^2)
+__device__ __forceinline__ double absval_of(double x, int what) { return what ? x * x : fabs(x); }
+__device__ __forceinline__ double absval_of(float x, int what) { return what ? (double)x * (double)x : fabs((double)x); }
+__device__ __forceinline__ double absval_of(z64 x, int what) { const double s = x.re * x.re + x.im * x.im; return what ? s : sqrt(s); }
+
+// Hand-over of values between the lanes of ONE wave through its own LDS slice: the hardware keeps a wave's LDS operations in order; the fences keep the
+// compiler from moving the LDS accesses of one side across to the other (release what was written, acquire before reading), the barrier its scheduler.
+__device__ __forceinline__ void wave_lds_handover() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// the larger of two values, NaN if either is one (a plain maximum would drop it: a matrix that holds a NaN must not report a finite norm)
+__device__ __forceinline__ double max_or_nan(double a, double b) { return b != b ? b : (a < b ? b : a); }
+
+constexpr int kStageElems = 1024;   // doubles of LDS per wave (column sums: one piece of a block; row sums: the lanes' accumulators at the end of a row)
+
+// Row sums, the elements of one block through the lanes of a wave.  A lane takes the 16-byte slots s = lane, lane + P, ... of the block; slot s holds the
+// elements V s - A ... V s - A + V - 1 (A = elements by which the block starts behind a 16-byte boundary, so every whole slot is one aligned access; the
+// first and the last slot may be cut by the block's ends and go element by element).  With V P a multiple of m the element rows a lane meets never change
+// inside a block row: accumulator k of lane l belongs to element row (V l + k - (V - 1)) mod m whatever A is, k = 0 ... 2 V - 2.
+template <typename T, int A>
+__device__ __forceinline__ void row_sum_slots(const T* __restrict__ d, int ne, int lane, int P, int vec_ok, int what, double (&acc)[2 * Pack16<T>::V - 1]) {
+  constexpr int V = Pack16<T>::V;
+  const int nslots = (ne + A + V - 1) / V;
+  for (int s = lane; s < nslots; s += P) {
+    const int e0 = V * s - A;
+    if (vec_ok && e0 >= 0 && e0 + V <= ne) {
+      const Pack16<T> x = *reinterpret_cast<const Pack16<T>*>(d + e0);
+#pragma unroll
+      for (int u = 0; u < V; ++u) acc[V - 1 - A + u] += absval_of(x.v[u], what);
+    } else {
+#pragma unroll
+      for (int u = 0; u < V; ++u)
+        if (e0 + u >= 0 && e0 + u < ne) acc[V - 1 - A + u] += absval_of(d[e0 + u], what);
+    }
+  }
+}
+
+// sum_j f(a_ij) per full row: S waves per block row, wave (row, sub) takes the blocks sub, sub + S, ... of the row and writes partials[sub * n_out + roff[row] + r]
+// for every element row r of the block row (zero when it met no block).  Every element is read once.  m / gcd(V, m) <= 64: the slot form above with
+// P = the largest multiple of m / gcd(V, m) that 64 lanes hold (23 x 23 doubles: 46 lanes, 16 bytes each); at the end of the row the accumulators go
+// through the wave's LDS slice and lane r adds those of its row in the order (k, lane).  Taller blocks: 64 element rows at a time, a lane per row, the
+// columns of every block one after the other (consecutive lanes read consecutive elements).
+template <typename T>
+__global__ void __launch_bounds__(256)
+algebra_row_sums(const int* __restrict__ row_p, const int* __restrict__ col_i, const int64_t* __restrict__ blk_p, const T* __restrict__ data,
+                 const int* __restrict__ rs, const int* __restrict__ cs, const int64_t* __restrict__ roff, int nbr, int S, int what, int vec_ok,
+                 int64_t n_out, double* __restrict__ partials) {
+  constexpr int V = Pack16<T>::V, K = 2 * V - 1;
+  __shared__ double red[4][K * 64];
+  const int lane = threadIdx.x & 63;
+  const int64_t wv = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int row = (int)(wv / S), sub = (int)(wv % S);
+  if (row >= nbr) return;
+  const int m = rs[row];
+  if (m <= 0) return;
+  const int64_t base = roff[row];
+  double* __restrict__ mine = partials + (size_t)sub * n_out;
+  const int b0 = row_p[row] + sub, b1 = row_p[row + 1];
+  const int g = V == 1 ? 1 : (m % V == 0 ? V : (m % 2 == 0 ? 2 : 1));   // gcd(V, m), V = 1, 2 or 4
+  const int p = m / g;
+  if (p > 64) {
+    for (int r0 = 0; r0 < m; r0 += 64) {
+      const int r = r0 + lane;
+      double acc = 0.0;
+      if (r < m)
+        for (int b = b0; b < b1; b += S) {
+          const int n = cs[col_i[b]];
+          const T* d = data + blk_p[b] + r;
+          for (int j = 0; j < n; ++j) acc += absval_of(d[(size_t)m * j], what);
+        }
+      if (r < m && base + r < n_out) mine[base + r] = acc;
+    }
+    return;
+  }
+  const int P = (64 / p) * p;
+  double acc[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) acc[k] = 0.0;
+  if (lane < P)
+    for (int b = b0; b < b1; b += S) {
+      const int ne = m * cs[col_i[b]];
+      const int64_t off = blk_p[b];
+      const T* d = data + off;
+      const int a = vec_ok ? (int)(off & (V - 1)) : 0;   // (wave-uniform)
+      if (V == 1 || a == 0) row_sum_slots<T, 0>(d, ne, lane, P, vec_ok, what, acc);
+      else if (a == 1) row_sum_slots<T, 1 % V>(d, ne, lane, P, vec_ok, what, acc);
+      else if (a == 2) row_sum_slots<T, 2 % V>(d, ne, lane, P, vec_ok, what, acc);
+      else row_sum_slots<T, 3 % V>(d, ne, lane, P, vec_ok, what, acc);
+    }
+  double* slice = red[threadIdx.x >> 6];
+#pragma unroll
+  for (int k = 0; k < K; ++k) slice[k * 64 + lane] = acc[k];
+  wave_lds_handover();   // (the slice is this wave's alone)
+  for (int r = lane; r < m; r += 64) {
+    double sum = 0.0;
+    for (int k = 0; k < K; ++k) {
+      // the lanes l with (V l + k - (V - 1)) mod m == r: the first one below the period p (found without touching LDS), then every p-th
+      int cur = ((k - (V - 1)) % m + m) % m, l0 = 0;
+      while (l0 < p && cur != r) {
+        ++l0;
+        cur += V;
+        if (cur >= m) cur -= m;
+        if (cur >= m) cur %= m;   // (m < V)
+      }
+      if (l0 < p)
+        for (int l = l0; l < P; l += p) sum += slice[k * 64 + l];
+    }
+    if (base + r < n_out) mine[base + r] = sum;
+  }
+}
+
+// out[i] = the sum of the S partial vectors in the order 0 ... S - 1, for i below *total (the full length, on the device); zero behind it
+__global__ void __launch_bounds__(256) algebra_vec_combine(const double* __restrict__ partials, int S, int64_t n_out, const int64_t* __restrict__ total,
+                                                           double* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_out) return;
+  double s = 0.0;
+  if (i < *total)
+    for (int k = 0; k < S; ++k) s += partials[(size_t)k * n_out + i];
+  out[i] = s;
+}
+
+// The blocks of every block column in ascending block-row order, built as the transpose builds its index (transpose_mark, row_prefix, the bitmap rank of
+// transpose_fill): list[2 t] = position of the source block in the matrix' index, list[2 t + 1] = its block row.  One wavefront per source block row.
+__global__ void __launch_bounds__(256) algebra_col_list(const int* __restrict__ row_p, const int* __restrict__ col_i, int nbr, int Wt,
+                                                        const uint32_t* __restrict__ t_bm, const int* __restrict__ t_pre, const int* __restrict__ col_p,
+                                                        int* __restrict__ list) {
+  const int lane = threadIdx.x & 63;
+  const int r = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (r >= nbr) return;
+  for (int b = row_p[r] + lane; b < row_p[r + 1]; b += 64) {
+    const size_t w = (size_t)col_i[b] * Wt + (r >> 5);
+    const int t = col_p[col_i[b]] + t_pre[w] + __popc(t_bm[w] & ((1u << (r & 31)) - 1u));
+    list[2 * (size_t)t] = b;
+    list[2 * (size_t)t + 1] = r;
+  }
+}
+
+// len <= kStageElems elements at d (element `off` of a 16-byte aligned area) -> f of them in lds[0 ... len), with aligned 16-byte loads where vec_ok
+template <typename T>
+__device__ __forceinline__ void stage_absval(const T* __restrict__ d, int64_t off, int len, int lane, int vec_ok, int what, double* lds) {
+  constexpr int V = Pack16<T>::V;
+  if (V > 1 && vec_ok) {
+    const int h = head_of<T>(off), head = h < len ? h : len, nv = (len - head) / V, done = head + nv * V;
+    if (lane < head) lds[lane] = absval_of(d[lane], what);
+    const Pack16<T>* dv = reinterpret_cast<const Pack16<T>*>(d + head);
+    for (int q = lane; q < nv; q += 64) {
+      const Pack16<T> x = dv[q];
+#pragma unroll
+      for (int u = 0; u < V; ++u) lds[head + q * V + u] = absval_of(x.v[u], what);
+    }
+    if (done + lane < len) lds[done + lane] = absval_of(d[done + lane], what);
+  } else {
+    for (int e = lane; e < len; e += 64) lds[e] = absval_of(d[e], what);
+  }
+}
+
+// the same loads, f summed per lane in a register (the lab build's ablation of the column sums without LDS)
+template <typename T>
+__device__ __forceinline__ double sum_absval(const T* __restrict__ d, int64_t off, int len, int lane, int vec_ok, int what) {
+  constexpr int V = Pack16<T>::V;
+  double s = 0.0;
+  if (V > 1 && vec_ok) {
+    const int h = head_of<T>(off), head = h < len ? h : len, nv = (len - head) / V, done = head + nv * V;
+    if (lane < head) s += absval_of(d[lane], what);
+    const Pack16<T>* dv = reinterpret_cast<const Pack16<T>*>(d + head);
+    for (int q = lane; q < nv; q += 64) {
+      const Pack16<T> x = dv[q];
+#pragma unroll
+      for (int u = 0; u < V; ++u) s += absval_of(x.v[u], what);
+    }
+    if (done + lane < len) s += absval_of(d[done + lane], what);
+  } else {
+    for (int e = lane; e < len; e += 64) s += absval_of(d[e], what);
+  }
+  return s;
+}
+
+// sum_i f(a_ij) per full column: S waves per block column walk its list (wave sub takes the entries sub, sub + S, ...); a block is one contiguous piece of
+// memory, column j of it the run j m ... j m + m - 1.  Lane j owns column j (64 columns at a time: of a wider block the wave reads, per pass, only the
+// part that holds its 64 columns, so every element is still read once).  A piece of up to kStageElems elements is loaded with coalesced 16-byte accesses,
+// f of it staged in the wave's LDS slice, and lane j adds what the piece holds of its run -- starting at element j mod (run length) of it and wrapping, so
+// that lanes whose runs lie a multiple of the bank count apart do not meet in one bank; the order is fixed all the same.  skip_diag: blocks on the block
+// diagonal do not count (the twin part of the Gershgorin sum of a stored triangle).
+// VARIANT 0 is what ships.  The others exist in the lab build only (DBCSR_AMD_ALG_COLSUMS, profiles/matrix_norms.txt): 1 stages a piece and reads one value
+// of it per lane (no add loop), 2 loads and adds in registers as algebra_norm2 does (no LDS), 3 walks no block at all (the list build, the launch and the sum
+// of the partial vectors remain) -- ablations, their results are not column sums --, 4 is the lane-per-column form without staging: lane j reads its run
+// from global memory element by element (a correct result, measured against 0).
+template <typename T, int VARIANT = 0>
+__global__ void __launch_bounds__(256)
+algebra_col_sums(const int* __restrict__ col_p, const int* __restrict__ list, const int64_t* __restrict__ blk_p, const T* __restrict__ data,
+                 const int* __restrict__ rs, const int* __restrict__ cs, const int64_t* __restrict__ coff, int nbc, int S, int what, int skip_diag,
+                 int vec_ok, int64_t n_out, double* __restrict__ partials) {
+  __shared__ double stage[4][kStageElems];
+  const int lane = threadIdx.x & 63;
+  const int64_t wv = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int c = (int)(wv / S), sub = (int)(wv % S);
+  if (c >= nbc) return;
+  const int n = cs[c];
+  const int64_t base = coff[c];
+  double* __restrict__ mine = partials + (size_t)sub * n_out;
+  double* lds = stage[threadIdx.x >> 6];
+  for (int j0 = 0; j0 < n; j0 += 64) {
+    const int nj = n - j0 < 64 ? n - j0 : 64;
+    double acc = 0.0;
+    for (int t = col_p[c] + sub; t < col_p[c + 1]; t += S) {
+      const int r = list[2 * (size_t)t + 1];
+      if (skip_diag && r == c) continue;
+      const int m = rs[r];
+      const int64_t off = blk_p[list[2 * (size_t)t]] + (int64_t)j0 * m;
+      const int total = nj * m, run0 = lane * m;   // the part of the block with this pass' columns; lane's run inside it
+      if constexpr (VARIANT == 3) continue;
+      if constexpr (VARIANT == 4) {
+        if (lane < nj) {
+          const T* run = data + off + run0;
+          for (int i = 0; i < m; ++i) acc += absval_of(run[i], what);
+        }
+        continue;
+      }
+      for (int c0 = 0; c0 < total; c0 += kStageElems) {
+        const int len = total - c0 < kStageElems ? total - c0 : kStageElems;
+        if constexpr (VARIANT == 2) {
+          acc += sum_absval(data + off + c0, off + c0, len, lane, vec_ok, what);
+          continue;
+        }
+        stage_absval(data + off + c0, off + c0, len, lane, vec_ok, what, lds);
+        wave_lds_handover();   // (the slice is this wave's alone)
+        if constexpr (VARIANT == 1) {
+          if (lane < len) acc += lds[lane];
+        } else {
+          const int lo = run0 > c0 ? run0 : c0, hi = run0 + m < c0 + len ? run0 + m : c0 + len;
+          if (lane < nj && lo < hi) {
+            const int cnt = hi - lo;
+            const double* run = lds + (lo - c0);
+            int i = lane % cnt;
+            for (int k = 0; k < cnt; ++k) {
+              acc += run[i];
+              if (++i == cnt) i = 0;
+            }
+          }
+        }
+        wave_lds_handover();   // (the next piece overwrites the slice)
+      }
+    }
+    if (lane < nj && base + j0 + lane < n_out) mine[base + j0 + lane] = acc;
+  }
+}
+
+template <typename T>
+__device__ __forceinline__ T wave_max(T x) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) x = max_or_nan(x, __shfl_down(x, off, 64));
+  return x;  // (lane 0's is the maximum; NaN if any lane's is)
+}
+
+// max |x| over the blocks the index names (holes do not count): as algebra_norm2, one partial per wave.  Real data: |x| itself, exact; complex data:
+// |x|^2, the root is taken once at the end (algebra_max_final).  A NaN among the elements comes out as NaN (max_or_nan), as it does of the sums
+__device__ __forceinline__ double maxterm_of(double x) { return fabs(x); }
+__device__ __forceinline__ double maxterm_of(float x) { return fabs((double)x); }
+__device__ __forceinline__ double maxterm_of(z64 x) { return x.re * x.re + x.im * x.im; }
+
+template <typename T>
+__global__ void __launch_bounds__(256) algebra_maxabs(const int* __restrict__ row_p, const int* __restrict__ col_i, const int64_t* __restrict__ blk_p,
+                                                      const T* __restrict__ data, const int* __restrict__ rs, const int* __restrict__ cs, int nbr, int S,
+                                                      int vec_ok, double* __restrict__ partials) {
+  constexpr int V = Pack16<T>::V;
+  const int lane = threadIdx.x & 63;
+  const int64_t wv = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int row = (int)(wv / S), sub = (int)(wv % S);
+  if (row >= nbr) return;
+  const int m = rs[row];
+  double acc = 0.0;
+  for (int b = row_p[row] + sub; b < row_p[row + 1]; b += S) {
+    const int ne = m * cs[col_i[b]];
+    const int64_t off = blk_p[b];
+    const T* d = data + off;
+    if (V > 1 && vec_ok) {
+      const int h = head_of<T>(off), head = h < ne ? h : ne, nv = (ne - head) / V, done = head + nv * V;
+      if (lane < head) acc = max_or_nan(acc, maxterm_of(d[lane]));
+      const Pack16<T>* dv = reinterpret_cast<const Pack16<T>*>(d + head);
+      for (int q = lane; q < nv; q += 64) {
+        const Pack16<T> x = dv[q];
+#pragma unroll
+        for (int u = 0; u < V; ++u) acc = max_or_nan(acc, maxterm_of(x.v[u]));
+      }
+      if (done + lane < ne) acc = max_or_nan(acc, maxterm_of(d[done + lane]));
+    } else {
+      for (int e = lane; e < ne; e += 64) acc = max_or_nan(acc, maxterm_of(d[e]));
+    }
+  }
+  acc = wave_max(acc);
+  if (lane == 0) partials[wv] = acc;
+}
+
+// one workgroup: *out = max_i (v[i] + w[i]) over n non-negative values (w == nullptr: v alone), its root with `root`; 0 for n == 0
+__global__ void __launch_bounds__(256) algebra_max_final(const double* __restrict__ v, const double* __restrict__ w, int64_t n, int root,
+                                                         double* __restrict__ out) {
+  __shared__ double best[256];
+  double x = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += 256) x = max_or_nan(x, v[i] + (w ? w[i] : 0.0));
+  best[threadIdx.x] = x;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off) best[threadIdx.x] = max_or_nan(best[threadIdx.x], best[threadIdx.x + off]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *out = root ? sqrt(best[0]) : best[0];
+}
+
+// The diagonal as a vector of the full-row length: one wavefront per block row.  get: the diagonal elements of the diagonal block the row has, zero where
+// it has none (or one that is not square: left alone, as diag_shift leaves it); one wavefront more writes zero behind the last row, so that every one of
+// the n elements is written.  set: the other way, onto the diagonal blocks present; nothing else is written.  Reads and writes of the vector stay below n.
+template <typename T>
+__global__ void __launch_bounds__(256) diag_get(const int* __restrict__ row_p, const int* __restrict__ col_i, const int64_t* __restrict__ blk_p,
+                                                const T* __restrict__ data, const int* __restrict__ rs, const int* __restrict__ cs,
+                                                const int64_t* __restrict__ roff, int nbr, T* __restrict__ out, int64_t n) {
+  const int lane = threadIdx.x & 63;
+  const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (row > nbr) return;
+  if (row == nbr) {
+    for (int64_t i = roff[nbr] + lane; i < n; i += 64) out[i] = T(0);
+    return;
+  }
+  const int at = find_diag_block(row_p, col_i, row, lane);
+  const int m = rs[row];
+  const bool have = at >= 0 && cs[row] == m;
+  const T* d = data + (have ? blk_p[at] : 0);
+  const int64_t base = roff[row];
+  for (int e = lane; e < m; e += 64)
+    if (base + e < n) out[base + e] = have ? d[(size_t)e * (m + 1)] : T(0);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) diag_set(const int* __restrict__ row_p, const int* __restrict__ col_i, const int64_t* __restrict__ blk_p,
+                                                const int* __restrict__ rs, const int* __restrict__ cs, const int64_t* __restrict__ roff, int nbr,
+                                                const T* __restrict__ vec, int64_t n, T* __restrict__ data) {
+  const int lane = threadIdx.x & 63;
+  const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (row >= nbr) return;
+  const int at = find_diag_block(row_p, col_i, row, lane);
+  if (at < 0) return;
+  const int m = rs[row];
+  if (cs[row] != m) return;   // (not a square block: never write outside the block)
+  T* d = data + blk_p[at];
+  const int64_t base = roff[row];
+  for (int e = lane; e < m; e += 64)
+    if (base + e < n) d[(size_t)e * (m + 1)] = vec[base + e];
+}
+
+// in place: a_ij <- a_ij * v[coff(c) + j] (side 1, right: `offs` = coff) or a_ij * v[roff(r) + i] (side 0, left: `offs` = roff).  By block row with S waves
+// per row as algebra_add_blocks, lanes over the elements with aligned 16-byte accesses; the position inside the block comes from one division per access.
+// An element whose entry of the vector would lie at n or behind stays as it is.
+template <typename T>
+__global__ void __launch_bounds__(256)
+algebra_scale_by_vector(const int* __restrict__ row_p, const int* __restrict__ col_i, const int64_t* __restrict__ blk_p, const int* __restrict__ rs,
+                        const int* __restrict__ cs, const int64_t* __restrict__ offs, int nbr, int S, int side, const T* __restrict__ vec, int64_t n,
+                        T* __restrict__ data, int vec_ok) {
+  constexpr int V = Pack16<T>::V;
+  const int lane = threadIdx.x & 63;
+  const int64_t wv = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int row = (int)(wv / S), sub = (int)(wv % S);
+  if (row >= nbr) return;
+  const int m = rs[row];
+  if (m <= 0) return;
+  for (int t = row_p[row] + sub; t < row_p[row + 1]; t += S) {
+    const int c = col_i[t], ne = m * cs[c];
+    const int64_t off = blk_p[t], vb = side ? offs[c] : offs[row];
+    T* d = data + off;
+    auto one = [&](int e) {
+      const int64_t idx = vb + (side ? e / m : e % m);
+      if (idx < n) d[e] = d[e] * vec[idx];
+    };
+    if (V == 1 || !vec_ok) {
+      for (int e = lane; e < ne; e += 64) one(e);
+      continue;
+    }
+    const int h = head_of<T>(off), head = h < ne ? h : ne, nv = (ne - head) / V, done = head + nv * V;
+    if (lane < head) one(lane);
+    Pack16<T>* dv = reinterpret_cast<Pack16<T>*>(d + head);
+    for (int q = lane; q < nv; q += 64) {
+      const int e = head + q * V;
+      int i = e % m, j = e / m;
+      Pack16<T> x = dv[q];
+#pragma unroll
+      for (int u = 0; u < V; ++u) {
+        const int64_t idx = vb + (side ? j : i);
+        if (idx < n) x.v[u] = x.v[u] * vec[idx];
+        if (++i == m) i = 0, ++j;
+      }
+      dv[q] = x;
+    }
+    if (done + lane < ne) one(done + lane);
+  }
+}
+
 }  // namespace dbcsr_amd
 #endif

@@ -1,6 +1,7 @@
 // mm_engine_algebra.h -- part of mm_engine.hip (included inside extern "C", after mm_engine_ops.h): the C-ABI operations between multiplies --
 // dbcsr_amd_bcsr_add_count / _add_apply, the pieces of dbcsr_add_on_diag (dbcsr_amd_bcsr_diag_count / _diag_fill / _diag_shift), dbcsr_amd_bcsr_trace,
-// _dot, _norm2.  Kernels: mm_algebra.h.  The reductions, the diagonal pieces and the same-pattern add use buffers of their own (Engine::alg_*) and the
+// _dot, _norm2, and the norms and vectors: dbcsr_amd_bcsr_maxabs, _row_sums, _col_sums, _gershgorin, _get_diag, _set_diag, _scale_by_vector.  Kernels:
+// mm_algebra.h.  The reductions, the diagonal pieces, the same-pattern add and the norms and vectors use buffers of their own (Engine::alg_*) and the
 // scan's scratch, which no saved plan depends on (the checksum uses it the same way): they do NOT invalidate the plan.  The union add borrows the
 // symbolic phase's bitmaps and prefix arrays and invalidates it, as filter and crop do.
 #ifndef DBCSR_AMD_MM_ENGINE_ALGEBRA_H
@@ -310,5 +311,232 @@ int dbcsr_amd_bcsr_dot(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd
   out[0] = two[0];
   return rc;
 }
+
+// ---- norms and vectors ---------------------------------------------------------------------------------------------------------------------------
+// Everything here works in Engine::alg_* and the scan's scratch: no entry invalidates the plan or writes a work area a saved plan depends on.
+extern "C++" {
+// element offsets of the block rows and columns (roff[nblkrows] / coff[nblkcols]: the full lengths), scanned on the device into alg_i64
+static int vector_offsets(Engine* E, hipStream_t st, const dbcsr_amd_bcsr* m, const int64_t** roff, const int64_t** coff) {
+  const size_t nbr = (size_t)m->nblkrows, nbc = (size_t)m->nblkcols;
+  if (E->alg_i64.ensure(8 + nbr + nbc + 2)) return -1;
+  int64_t* r = E->alg_i64.p + 8;
+  int64_t* c = r + nbr + 1;
+  if (exclusive_scan<int64_t>(E, m->row_blk_size, (int64_t)nbr, r, nullptr, true, st)) return -1;
+  if (exclusive_scan<int64_t>(E, m->col_blk_size, (int64_t)nbc, c, nullptr, true, st)) return -1;
+  *roff = r;
+  *coff = c;
+  return 0;
+}
+
+// the blocks of every block column in ascending block-row order (alg_col_p, alg_list), as transpose_any forms a transposed index -- in buffers of the algebra
+static int col_list_build(Engine* E, hipStream_t st, const dbcsr_amd_bcsr* a) {
+  const int nbr = a->nblkrows, nbc = a->nblkcols, Wt = (nbr + 31) / 32;
+  const size_t nw = (size_t)nbc * Wt;
+  if (E->alg_bm.ensure(nw + 1) || E->alg_pre.ensure(nw + 1) || E->alg_cnt.ensure((size_t)nbc + 1) || E->alg_col_p.ensure((size_t)nbc + 2) ||
+      E->alg_list.ensure(2 * (size_t)a->nblks + 2))
+    return -1;
+  ACC_CHECK(hipMemsetAsync(E->alg_bm.p, 0, sizeof(uint32_t) * (nw + 1), st));
+  hipLaunchKernelGGL(transpose_mark, grid_for((int64_t)nbr * 64), dim3(256), 0, st, a->row_p, a->col_i, nbr, Wt, E->alg_bm.p);
+  hipLaunchKernelGGL(row_prefix, grid_for((int64_t)nbc * 64), dim3(256), 0, st, E->alg_bm.p, nbc, Wt, E->alg_pre.p, E->alg_cnt.p);
+  if (exclusive_scan<int32_t>(E, E->alg_cnt.p, nbc, E->alg_col_p.p, nullptr, true, st)) return -1;
+  hipLaunchKernelGGL(algebra_col_list, grid_for((int64_t)nbr * 64), dim3(256), 0, st, a->row_p, a->col_i, nbr, Wt, E->alg_bm.p, E->alg_pre.p,
+                     E->alg_col_p.p, E->alg_list.p);
+  return 0;
+}
+
+// (the callers made alg_sums hold S * n_out doubles)
+template <typename T>
+static void row_sums_launch(Engine* E, hipStream_t st, const dbcsr_amd_bcsr* a, int what, const int64_t* roff, double* out, int64_t n_out) {
+  const int nbr = a->nblkrows, S = row_split(nbr, a->nblks);
+  hipLaunchKernelGGL((algebra_row_sums<T>), grid_for((int64_t)nbr * S * 64), dim3(256), 0, st, a->row_p, a->col_i, a->blk_p,
+                     static_cast<const T*>(a->data), a->row_blk_size, a->col_blk_size, roff, nbr, S, what, aligned16(a->data), n_out, E->alg_sums.p);
+  hipLaunchKernelGGL(algebra_vec_combine, grid_for(n_out), dim3(256), 0, st, E->alg_sums.p, S, n_out, roff + nbr, out);
+}
+
+template <typename T>
+static void col_sums_launch(Engine* E, hipStream_t st, const dbcsr_amd_bcsr* a, int what, int skip_diag, const int64_t* coff, double* out, int64_t n_out) {
+  const int nbc = a->nblkcols, S = row_split(nbc, a->nblks);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid_for((int64_t)nbc * S * 64), dim3(256), 0, st, E->alg_col_p.p, E->alg_list.p, a->blk_p, static_cast<const T*>(a->data),
+                       a->row_blk_size, a->col_blk_size, coff, nbc, S, what, skip_diag, aligned16(a->data), n_out, E->alg_sums.p);
+  };
+#ifdef DBCSR_AMD_EXPERIMENTS
+  switch (E->ls.alg_col_variant) {   // DBCSR_AMD_ALG_COLSUMS: ablations and the lane-per-column form (mm_algebra.h)
+    case 1: launch(algebra_col_sums<T, 1>); break;
+    case 2: launch(algebra_col_sums<T, 2>); break;
+    case 3: launch(algebra_col_sums<T, 3>); break;
+    case 4: launch(algebra_col_sums<T, 4>); break;
+    default: launch(algebra_col_sums<T, 0>);
+  }
+#else
+  launch(algebra_col_sums<T, 0>);
+#endif
+  hipLaunchKernelGGL(algebra_vec_combine, grid_for(n_out), dim3(256), 0, st, E->alg_sums.p, S, n_out, coff + nbc, out);
+}
+
+template <typename T>
+static void maxabs_launch(Engine* E, hipStream_t st, const dbcsr_amd_bcsr* a, int S) {
+  const int nbr = a->nblkrows;
+  hipLaunchKernelGGL((algebra_maxabs<T>), grid_for((int64_t)nbr * S * 64), dim3(256), 0, st, a->row_p, a->col_i, a->blk_p, static_cast<const T*>(a->data),
+                     a->row_blk_size, a->col_blk_size, nbr, S, aligned16(a->data), E->alg_sums.p);
+}
+
+template <typename T>
+static void diag_vector_launch(hipStream_t st, bool set, const dbcsr_amd_bcsr* m, const int64_t* roff, void* vec, int64_t n) {
+  const int nbr = m->nblkrows;
+  if (set)
+    hipLaunchKernelGGL((diag_set<T>), grid_for((int64_t)nbr * 64), dim3(256), 0, st, m->row_p, m->col_i, m->blk_p, m->row_blk_size, m->col_blk_size, roff, nbr,
+                       static_cast<const T*>(vec), n, static_cast<T*>(m->data));
+  else
+    hipLaunchKernelGGL((diag_get<T>), grid_for(((int64_t)nbr + 1) * 64), dim3(256), 0, st, m->row_p, m->col_i, m->blk_p, static_cast<const T*>(m->data),
+                       m->row_blk_size, m->col_blk_size, roff, nbr, static_cast<T*>(vec), n);
+}
+
+template <typename T>
+static void scale_by_vector_launch(hipStream_t st, const dbcsr_amd_bcsr* m, const int64_t* offs, int side, const void* vec, int64_t n) {
+  const int nbr = m->nblkrows, S = algebra_split(nbr, m->nblks);
+  hipLaunchKernelGGL((algebra_scale_by_vector<T>), grid_for((int64_t)nbr * S * 64), dim3(256), 0, st, m->row_p, m->col_i, m->blk_p, m->row_blk_size,
+                     m->col_blk_size, offs, nbr, S, side, static_cast<const T*>(vec), n, static_cast<T*>(m->data), aligned16(m->data));
+}
+
+// one double on the device brought to the host (synchronises)
+static int scalar_finish(Engine* E, hipStream_t st, const double* dev, double out[1], const char* what) {
+  ACC_CHECK(hipMemcpyAsync(E->host_scalars + 4, dev, sizeof(double), hipMemcpyDeviceToHost, st));
+  ACC_CHECK(hipStreamSynchronize(st));
+  memcpy(out, E->host_scalars + 4, sizeof(double));
+  return check(hipGetLastError(), what, __FILE__, __LINE__);
+}
+}  // extern "C++"
+
+#define DBCSR_AMD_BY_TYPE(F, ...)                                              \
+  do {                                                                         \
+    if (datatype == dbcsr_type_real_8) F<double>(__VA_ARGS__);                 \
+    else if (datatype == dbcsr_type_real_4) F<float>(__VA_ARGS__);             \
+    else F<z64>(__VA_ARGS__);                                                  \
+  } while (0)
+
+int dbcsr_amd_bcsr_maxabs(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, double out[1], void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E || !m || !out) return -1;
+  if (!algebra_type(datatype)) return -10;
+  hipStream_t st = stream_of(stream);
+  out[0] = 0.0;
+  if (m->nblkrows == 0 || m->nblks == 0) return 0;
+  const int S = row_split(m->nblkrows, m->nblks);
+  const int64_t nw = (int64_t)m->nblkrows * S;
+  if (E->alg_sums.ensure((size_t)nw + 2)) return -1;
+  DBCSR_AMD_BY_TYPE(maxabs_launch, E, st, m, S);
+  hipLaunchKernelGGL(algebra_max_final, dim3(1), dim3(256), 0, st, E->alg_sums.p, (const double*)nullptr, nw, datatype == dbcsr_type_complex_8 ? 1 : 0,
+                     E->alg_sums.p + nw);
+  return scalar_finish(E, st, E->alg_sums.p + nw, out, "dbcsr_amd_bcsr_maxabs");
+}
+
+int dbcsr_amd_bcsr_row_sums(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, int what, double* out, int64_t n_out, void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E || !m || n_out < 0 || (n_out > 0 && !out) || (what != 0 && what != 1)) return -1;
+  if (!algebra_type(datatype)) return -10;
+  hipStream_t st = stream_of(stream);
+  if (n_out == 0) return 0;
+  if (m->nblkrows == 0 || m->nblks == 0) {
+    ACC_CHECK(hipMemsetAsync(out, 0, sizeof(double) * (size_t)n_out, st));
+    return 0;
+  }
+  const int64_t *roff = nullptr, *coff = nullptr;
+  if (E->alg_sums.ensure((size_t)row_split(m->nblkrows, m->nblks) * n_out + 2) || vector_offsets(E, st, m, &roff, &coff)) return -1;
+  DBCSR_AMD_BY_TYPE(row_sums_launch, E, st, m, what, roff, out, n_out);
+  return check(hipGetLastError(), "dbcsr_amd_bcsr_row_sums", __FILE__, __LINE__);
+}
+
+int dbcsr_amd_bcsr_col_sums(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, int what, int skip_diagonal_blocks, double* out,
+                            int64_t n_out, void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E || !m || n_out < 0 || (n_out > 0 && !out) || (what != 0 && what != 1)) return -1;
+  if (!algebra_type(datatype)) return -10;
+  hipStream_t st = stream_of(stream);
+  if (n_out == 0) return 0;
+  if (m->nblkrows == 0 || m->nblkcols == 0 || m->nblks == 0) {
+    ACC_CHECK(hipMemsetAsync(out, 0, sizeof(double) * (size_t)n_out, st));
+    return 0;
+  }
+  const int64_t *roff = nullptr, *coff = nullptr;
+  if (E->alg_sums.ensure((size_t)row_split(m->nblkcols, m->nblks) * n_out + 2) || vector_offsets(E, st, m, &roff, &coff) || col_list_build(E, st, m))
+    return -1;
+  DBCSR_AMD_BY_TYPE(col_sums_launch, E, st, m, what, skip_diagonal_blocks ? 1 : 0, coff, out, n_out);
+  return check(hipGetLastError(), "dbcsr_amd_bcsr_col_sums", __FILE__, __LINE__);
+}
+
+int dbcsr_amd_bcsr_gershgorin(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, int symmetric, double out[1], void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E || !m || !out || (symmetric && m->nblkrows != m->nblkcols)) return -1;
+  if (!algebra_type(datatype)) return -10;
+  hipStream_t st = stream_of(stream);
+  out[0] = 0.0;
+  if (m->nblkrows == 0 || m->nblkcols == 0 || m->nblks == 0) return 0;
+  const int64_t *roff = nullptr, *coff = nullptr;
+  if (vector_offsets(E, st, m, &roff, &coff)) return -1;
+  // the full row count sizes the vectors: known from an earlier call with these block sizes, fetched otherwise (then this call synchronises twice)
+  int64_t n = -1;
+  if (m->index_stamp != 0)
+    for (const Engine::AlgLen& k : E->alg_len)
+      if (k.stamp == m->index_stamp && k.rs == m->row_blk_size && k.cs == m->col_blk_size && k.nbr == m->nblkrows && k.nbc == m->nblkcols) n = k.rows;
+  if (n < 0) {
+    ACC_CHECK(hipMemcpyAsync(E->host_scalars + 6, roff + m->nblkrows, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    ACC_CHECK(hipStreamSynchronize(st));
+    n = E->host_scalars[6];
+    if (m->index_stamp != 0) {
+      Engine::AlgLen& k = E->alg_len[E->alg_len_next];
+      E->alg_len_next = (E->alg_len_next + 1) % Engine::kAlgLens;
+      k.rs = m->row_blk_size, k.cs = m->col_blk_size, k.stamp = m->index_stamp, k.nbr = m->nblkrows, k.nbc = m->nblkcols, k.rows = n;
+    }
+  }
+  if (n <= 0) return 0;
+  const int S = std::max(row_split(m->nblkrows, m->nblks), symmetric ? row_split(m->nblkcols, m->nblks) : 1);
+  if (E->alg_vec.ensure(2 * (size_t)n + 2) || E->alg_sums.ensure((size_t)S * n + 2)) return -1;
+  double* rows = E->alg_vec.p;
+  double* cols = symmetric ? rows + n : nullptr;
+  if (symmetric && col_list_build(E, st, m)) return -1;
+  DBCSR_AMD_BY_TYPE(row_sums_launch, E, st, m, 0, roff, rows, n);
+  if (symmetric) DBCSR_AMD_BY_TYPE(col_sums_launch, E, st, m, 0, 1, coff, cols, n);   // the twins of the stored blocks off the diagonal
+  hipLaunchKernelGGL(algebra_max_final, dim3(1), dim3(256), 0, st, rows, (const double*)cols, n, 0, rows + 2 * n);
+  return scalar_finish(E, st, rows + 2 * n, out, "dbcsr_amd_bcsr_gershgorin");
+}
+
+static int diag_vector(void* handle, libsmm_acc_data_t datatype, bool set, const dbcsr_amd_bcsr* m, void* vec, int64_t n, void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E || !m || n < 0 || (n > 0 && !vec) || m->nblkrows != m->nblkcols) return -1;
+  if (!algebra_type(datatype)) return -10;
+  hipStream_t st = stream_of(stream);
+  if (n == 0) return 0;
+  const size_t esize = datatype == dbcsr_type_real_8 ? 8 : datatype == dbcsr_type_real_4 ? 4 : 16;
+  if (m->nblkrows == 0 || m->nblks == 0) {
+    if (!set) ACC_CHECK(hipMemsetAsync(vec, 0, esize * (size_t)n, st));
+    return 0;
+  }
+  const int64_t *roff = nullptr, *coff = nullptr;
+  if (vector_offsets(E, st, m, &roff, &coff)) return -1;
+  DBCSR_AMD_BY_TYPE(diag_vector_launch, st, set, m, roff, vec, n);
+  return check(hipGetLastError(), set ? "dbcsr_amd_bcsr_set_diag" : "dbcsr_amd_bcsr_get_diag", __FILE__, __LINE__);
+}
+
+int dbcsr_amd_bcsr_get_diag(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, void* diag, int64_t n, void* stream) {
+  return diag_vector(handle, datatype, false, m, diag, n, stream);
+}
+
+int dbcsr_amd_bcsr_set_diag(void* handle, libsmm_acc_data_t datatype, dbcsr_amd_bcsr* m, const void* diag, int64_t n, void* stream) {
+  return diag_vector(handle, datatype, true, m, const_cast<void*>(diag), n, stream);
+}
+
+int dbcsr_amd_bcsr_scale_by_vector(void* handle, libsmm_acc_data_t datatype, dbcsr_amd_bcsr* m, const void* vec, int64_t n, int side, void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E || !m || n < 0 || (n > 0 && !vec) || (side != 0 && side != 1)) return -1;
+  if (!algebra_type(datatype)) return -10;
+  hipStream_t st = stream_of(stream);
+  if (n == 0 || m->nblkrows == 0 || m->nblks == 0) return 0;
+  const int64_t *roff = nullptr, *coff = nullptr;
+  if (vector_offsets(E, st, m, &roff, &coff)) return -1;
+  DBCSR_AMD_BY_TYPE(scale_by_vector_launch, st, m, side ? coff : roff, side, vec, n);
+  return check(hipGetLastError(), "dbcsr_amd_bcsr_scale_by_vector", __FILE__, __LINE__);
+}
+#undef DBCSR_AMD_BY_TYPE
 
 #endif

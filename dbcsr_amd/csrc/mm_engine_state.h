@@ -63,6 +63,9 @@ struct LabState {
   unsigned hot_xcd_mask = 0xffu;  // DBCSR_AMD_MM_HOT_XCDS: XCDs the persistent form runs on (experiments: the others' C blocks are NOT computed)
   DevBuf<unsigned> hot_counters;
 
+  // norms and vectors: DBCSR_AMD_ALG_COLSUMS = 1 ... 4, the ablations of algebra_col_sums and its lane-per-column form (mm_algebra.h)
+  int alg_col_variant = 0;
+
   void forget_plan() { tile_built = band_built = group_built = false; }
 };
 #endif
@@ -120,9 +123,25 @@ struct Engine {
 
   // ---- matrix algebra (mm_engine_algebra.h): buffers of its own, nothing a saved plan depends on.  Only the general (union) add borrows the symbolic
   // work areas, and invalidates the plan ----
-  DevBuf<double> alg_sums;    // reductions: one pair of doubles per wave, the result behind them
+  DevBuf<double> alg_sums;    // reductions: one pair of doubles per wave, the result behind them; norms and vectors: S partial vectors of n doubles / one maximum per wave
   DevBuf<int> alg_i32;        // [0] flags of algebra_compare; diag: need[nbr], blk_nze[nbr]
-  DevBuf<int64_t> alg_i64;    // [0 ... 7] scalars; diag: offsets of the missing diagonal blocks
+  DevBuf<int64_t> alg_i64;    // [0 ... 7] scalars; diag: offsets of the missing diagonal blocks; norms and vectors: element offsets of block rows / columns
+  // norms and vectors: the per-column block lists (a transposed index: bitmap, prefix, counts, column pointers, (block, row) pairs) and Gershgorin's vectors
+  DevBuf<uint32_t> alg_bm;
+  DevBuf<int> alg_pre, alg_cnt, alg_col_p, alg_list;
+  DevBuf<double> alg_vec;     // Gershgorin: row sums [n], column sums [n], the result
+  // dbcsr_amd_bcsr_gershgorin sizes its vectors by the full row count, which only the device knows: the counts of the last few sets of block sizes it saw
+  // (same size arrays, same non-zero index_stamp), so that an iteration over a few matrices fetches each count once
+  struct AlgLen {
+    const void* rs = nullptr;
+    const void* cs = nullptr;
+    uint64_t stamp = 0;
+    int nbr = 0, nbc = 0;
+    int64_t rows = 0;
+  };
+  static constexpr int kAlgLens = 8;
+  AlgLen alg_len[kAlgLens];
+  int alg_len_next = 0;
   int add_mode = 0;           // what the last dbcsr_amd_bcsr_add_count found: 0 nothing pending, 1 same pattern (flat pass), 2 union pattern
   int add_beta_zero = 0;
   int64_t add_nblks_a = 0, add_nblks_b = 0, add_nblks = 0, add_nze = 0;

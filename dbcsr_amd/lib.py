@@ -42,6 +42,9 @@ MM_SYMBOLS = [
     # matrix algebra between multiplies (dbcsr_amd/operations.py)
     "dbcsr_amd_bcsr_add_count", "dbcsr_amd_bcsr_add_apply", "dbcsr_amd_bcsr_diag_count", "dbcsr_amd_bcsr_diag_fill", "dbcsr_amd_bcsr_diag_shift",
     "dbcsr_amd_bcsr_trace", "dbcsr_amd_bcsr_dot", "dbcsr_amd_bcsr_norm2",
+    # norms and vectors
+    "dbcsr_amd_bcsr_maxabs", "dbcsr_amd_bcsr_row_sums", "dbcsr_amd_bcsr_col_sums", "dbcsr_amd_bcsr_gershgorin", "dbcsr_amd_bcsr_get_diag",
+    "dbcsr_amd_bcsr_set_diag", "dbcsr_amd_bcsr_scale_by_vector",
 ]
 
 # `kind` of a matrix with symmetry in the C ABI (include/dbcsr_amd_mm.h): bit 0 negates the twin block, bit 1 conjugates it
@@ -195,6 +198,13 @@ def load_library(lab=False):
     L.dbcsr_amd_bcsr_trace.argtypes = [vp, i32, BP, Z, vp]
     L.dbcsr_amd_bcsr_dot.argtypes = [vp, i32, BP, BP, i32, Z, vp]
     L.dbcsr_amd_bcsr_norm2.argtypes = [vp, i32, BP, i32, Z, vp]
+    L.dbcsr_amd_bcsr_maxabs.argtypes = [vp, i32, BP, Z, vp]
+    L.dbcsr_amd_bcsr_row_sums.argtypes = [vp, i32, BP, i32, vp, i64, vp]
+    L.dbcsr_amd_bcsr_col_sums.argtypes = [vp, i32, BP, i32, i32, vp, i64, vp]
+    L.dbcsr_amd_bcsr_gershgorin.argtypes = [vp, i32, BP, i32, Z, vp]
+    L.dbcsr_amd_bcsr_get_diag.argtypes = [vp, i32, BP, vp, i64, vp]
+    L.dbcsr_amd_bcsr_set_diag.argtypes = [vp, i32, BP, vp, i64, vp]
+    L.dbcsr_amd_bcsr_scale_by_vector.argtypes = [vp, i32, BP, vp, i64, i32, vp]
     if lab:   # diagnostics of the experimental dataflows (dbcsr_amd/csrc/mm_lab_api.h): the shipping build does not export them
         L.dbcsr_amd_mm_tile_stats.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
         L.dbcsr_amd_mm_band_stats.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]

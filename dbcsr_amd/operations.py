@@ -7,6 +7,11 @@
     dbcsr_trace(matrix)                                         sum of the diagonal elements
     dbcsr_dot(matrix_a, matrix_b)                               sum a_ij * b_ij = trace(A^T B)          (real data)
     dbcsr_frobenius_norm(matrix)                                sqrt(sum |x|^2)
+    dbcsr_maxabs_norm(matrix)                                   max |x|
+    dbcsr_gershgorin_norm(matrix)                               max_i sum_j |a_ij|
+    dbcsr_norm(matrix, which_norm, norm_vector)                 one of the three, or the column norms sqrt(sum_i |a_ij|^2)
+    dbcsr_get_diag(matrix) / dbcsr_set_diag(matrix, diag)       the diagonal as a device vector
+    dbcsr_scale_by_vector(matrix, alpha, side)                  A <- A*diag(alpha) ("right") or diag(alpha)*A ("left")
 
 Same argument names and error behaviour; the work is done by the C-ABI engine (include/dbcsr_amd_mm.h, "Matrix algebra between
 multiplies") on the GPU, for float64, float32 and complex128 data.  One rank / one device here: of a distributed matrix trace, dot
@@ -16,10 +21,16 @@ import math
 
 import torch
 
-from .matrix import DbcsrMatrix, StreamHandle
+from .matrix import DbcsrMatrix, StreamHandle, _serial
 from .multiply import _z, default_engine
 
 _SYMMETRIES = ("N", "S", "A", "H", "K")
+
+# which_norm of dbcsr_norm (the reference's constants)
+dbcsr_norm_frobenius = 1
+dbcsr_norm_maxabsnorm = 2
+dbcsr_norm_gershgorin = 3
+dbcsr_norm_column = 4
 
 
 def _check_symmetry(name, m):
@@ -190,3 +201,153 @@ def dbcsr_frobenius_norm(matrix, engine=None, stream=None):
     if rc != 0:
         raise RuntimeError("dbcsr_amd_bcsr_norm2 failed (%d)" % rc)
     return math.sqrt(out[0])
+
+
+# ---- norms and vectors --------------------------------------------------------------------------------------------------------------------------
+_FULL_SIZES = {}   # (serial, version) of a block-size tensor -> its sum: the length of a vector over the full rows / columns
+
+
+def _full_size(sizes):
+    key = (_serial(sizes), sizes._version)
+    n = _FULL_SIZES.get(key)
+    if n is None:
+        if len(_FULL_SIZES) > 256:
+            _FULL_SIZES.clear()
+        n = _FULL_SIZES[key] = int(sizes.sum().item()) if sizes.numel() else 0
+    return n
+
+
+def _check_square(name, matrix):
+    rs, cs = matrix.row_blk_size, matrix.col_blk_size
+    if matrix.nblkrows != matrix.nblkcols or not (rs is cs or torch.equal(rs, cs)):
+        raise ValueError("%s: the matrix is not square (row and column block sizes differ)" % name)
+
+
+def _check_vector(name, matrix, vec, n, dtype=None):
+    """a device vector of n elements of the matrix' data type (or `dtype`), contiguous: checked before any call of the library"""
+    if not isinstance(vec, torch.Tensor):
+        raise TypeError("%s: the vector must be a torch tensor" % name)
+    if vec.dtype != (dtype or matrix.dtype):
+        raise TypeError("%s: the vector has data type %r, expected %r" % (name, vec.dtype, dtype or matrix.dtype))
+    if vec.device != matrix.row_p.device:
+        raise ValueError("%s: the vector is not on the matrix' device" % name)
+    if vec.dim() != 1 or vec.numel() != n or not vec.is_contiguous():
+        raise ValueError("%s: the vector must be contiguous with %d elements" % (name, n))
+
+
+def dbcsr_maxabs_norm(matrix, engine=None, stream=None):
+    """max |x| over the stored blocks (dbcsr_maxabs_norm); the modulus for complex data."""
+    _check_symmetry("dbcsr_maxabs_norm", matrix)
+    E = engine or default_engine()
+    st = StreamHandle(stream)
+    out = (C.c_double * 2)()
+    d = matrix.desc()
+    rc = E.L.dbcsr_amd_bcsr_maxabs(E.h, matrix.dtype_code, C.byref(d), out, st.ptr)
+    if rc != 0:
+        raise RuntimeError("dbcsr_amd_bcsr_maxabs failed (%d)" % rc)
+    return out[0]
+
+
+def dbcsr_gershgorin_norm(matrix, engine=None, stream=None):
+    """max over the full rows of sum_j |a_ij| (dbcsr_gershgorin_norm).  With symmetry 'S', 'A', 'H', 'K' a stored block off the diagonal
+    also adds its column sums to the rows of its twin: the value is that of the desymmetrized matrix."""
+    sym = _check_symmetry("dbcsr_gershgorin_norm", matrix)
+    if sym != "N":
+        _check_square("dbcsr_gershgorin_norm", matrix)
+    E = engine or default_engine()
+    st = StreamHandle(stream)
+    out = (C.c_double * 2)()
+    d = matrix.desc()
+    rc = E.L.dbcsr_amd_bcsr_gershgorin(E.h, matrix.dtype_code, C.byref(d), 0 if sym == "N" else 1, out, st.ptr)
+    if rc != 0:
+        raise RuntimeError("dbcsr_amd_bcsr_gershgorin failed (%d)" % rc)
+    return out[0]
+
+
+def dbcsr_norm(matrix, which_norm, norm_vector=None, engine=None, stream=None):
+    """dbcsr_norm: which_norm = dbcsr_norm_frobenius, dbcsr_norm_maxabsnorm or dbcsr_norm_gershgorin returns the scalar;
+    dbcsr_norm_column returns a float64 device tensor with sqrt(sum_i |a_ij|^2) per full column (norm_vector, when given, is filled and
+    returned).  The column norms are offered for symmetry 'N' only (NotImplementedError otherwise: how the reference treats the twin blocks
+    there could not be checked, and it is not guessed)."""
+    if which_norm == dbcsr_norm_frobenius:
+        return dbcsr_frobenius_norm(matrix, engine=engine, stream=stream)
+    if which_norm == dbcsr_norm_maxabsnorm:
+        return dbcsr_maxabs_norm(matrix, engine=engine, stream=stream)
+    if which_norm == dbcsr_norm_gershgorin:
+        return dbcsr_gershgorin_norm(matrix, engine=engine, stream=stream)
+    if which_norm != dbcsr_norm_column:
+        raise ValueError("dbcsr_norm: unknown which_norm %r" % (which_norm,))
+    sym = _check_symmetry("dbcsr_norm", matrix)
+    if sym != "N":
+        raise NotImplementedError("dbcsr_norm: column norms of a matrix with symmetry %r" % sym)
+    matrix.dtype_code
+    n = _full_size(matrix.col_blk_size)
+    if norm_vector is not None:
+        _check_vector("dbcsr_norm", matrix, norm_vector, n, torch.float64)
+    E = engine or default_engine()
+    st = StreamHandle(stream)
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        out = norm_vector if norm_vector is not None else torch.empty(n, dtype=torch.float64, device=matrix.row_p.device)
+        d = matrix.desc()
+        rc = E.L.dbcsr_amd_bcsr_col_sums(E.h, matrix.dtype_code, C.byref(d), 1, 0, out.data_ptr() if n else None, n, st.ptr)
+        if rc != 0:
+            raise RuntimeError("dbcsr_amd_bcsr_col_sums failed (%d)" % rc)
+        torch.sqrt(out, out=out)   # (one root per column of the vector the kernels made)
+    return out
+
+
+def dbcsr_get_diag(matrix, engine=None, stream=None):
+    """The diagonal as a device tensor of the matrix' data type and full-row length (dbcsr_get_diag): the diagonal elements of the diagonal
+    blocks present, zero where a block row has no diagonal block.  Any symmetry: what is stored is read."""
+    _check_symmetry("dbcsr_get_diag", matrix)
+    _check_square("dbcsr_get_diag", matrix)
+    matrix.dtype_code
+    n = _full_size(matrix.row_blk_size)
+    E = engine or default_engine()
+    st = StreamHandle(stream)
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        out = torch.empty(n, dtype=matrix.dtype, device=matrix.row_p.device)
+    d = matrix.desc()
+    rc = E.L.dbcsr_amd_bcsr_get_diag(E.h, matrix.dtype_code, C.byref(d), out.data_ptr() if n else None, n, st.ptr)
+    if rc != 0:
+        raise RuntimeError("dbcsr_amd_bcsr_get_diag failed (%d)" % rc)
+    return out
+
+
+def dbcsr_set_diag(matrix, diag, engine=None, stream=None):
+    """a_ii <- diag[i] (dbcsr_set_diag), in place.  Only the diagonal blocks PRESENT are written: no block is created and nothing else is
+    touched (the matrix keeps its index and its index_stamp()); dbcsr_add_on_diag(matrix, 0.0) creates the missing diagonal blocks first.
+    Square matrices with symmetry 'N', 'S' or 'H'; diag: a device tensor of the matrix' data type and full-row length."""
+    sym = _check_symmetry("dbcsr_set_diag", matrix)
+    if sym in ("A", "K"):
+        raise ValueError("dbcsr_set_diag: not defined for an antisymmetric / antihermitian matrix (symmetry %r)" % sym)
+    _check_square("dbcsr_set_diag", matrix)
+    matrix.dtype_code
+    n = _full_size(matrix.row_blk_size)
+    _check_vector("dbcsr_set_diag", matrix, diag, n)
+    E = engine or default_engine()
+    st = StreamHandle(stream)
+    d = matrix.desc()   # (only the data area is written)
+    rc = E.L.dbcsr_amd_bcsr_set_diag(E.h, matrix.dtype_code, C.byref(d), diag.data_ptr() if n else None, n, st.ptr)
+    if rc != 0:
+        raise RuntimeError("dbcsr_amd_bcsr_set_diag failed (%d)" % rc)
+
+
+def dbcsr_scale_by_vector(matrix, alpha, side, engine=None, stream=None):
+    """A <- A * diag(alpha) (side = "right": column j times alpha[j]) or diag(alpha) * A (side = "left": row i times alpha[i]), in place
+    (dbcsr_scale_by_vector).  alpha: a device tensor of the matrix' data type with one element per full column / row.  Symmetry 'N' only:
+    a stored triangle scaled on one side is not a matrix with that symmetry."""
+    if side not in ("left", "right"):
+        raise ValueError("dbcsr_scale_by_vector: side must be 'left' or 'right', got %r" % (side,))
+    sym = _check_symmetry("dbcsr_scale_by_vector", matrix)
+    if sym != "N":
+        raise ValueError("dbcsr_scale_by_vector: not defined for a matrix with symmetry %r" % sym)
+    matrix.dtype_code
+    n = _full_size(matrix.col_blk_size if side == "right" else matrix.row_blk_size)
+    _check_vector("dbcsr_scale_by_vector", matrix, alpha, n)
+    E = engine or default_engine()
+    st = StreamHandle(stream)
+    d = matrix.desc()   # (only the data area is written)
+    rc = E.L.dbcsr_amd_bcsr_scale_by_vector(E.h, matrix.dtype_code, C.byref(d), alpha.data_ptr() if n else None, n, 1 if side == "right" else 0, st.ptr)
+    if rc != 0:
+        raise RuntimeError("dbcsr_amd_bcsr_scale_by_vector failed (%d)" % rc)

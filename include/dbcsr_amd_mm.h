@@ -342,6 +342,39 @@ int dbcsr_amd_bcsr_dot(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd
   void* stream);
 int dbcsr_amd_bcsr_norm2(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, int symmetric, double out[1], void* stream);
 
+/* Norms and vectors (src/ops/dbcsr_operations.F: dbcsr_norm / dbcsr_gershgorin_norm / dbcsr_maxabs_norm, dbcsr_get_diag, dbcsr_set_diag,
+ * dbcsr_scale_by_vector): a result or an operand per FULL row or column of the matrix.  Same types, same answers as above (-10, -1; 0 for an empty matrix:
+ * scalar outputs are then 0, the vector outputs of the sums and of _get_diag all zero).  out, diag and vec are DEVICE memory.  A vector over the rows has
+ * sum(row_blk_size) elements, one over the columns sum(col_blk_size), in the order of the dense matrix; the element offsets of the block rows / columns are
+ * formed on the device.  Sums are carried in double, one partial vector per wave of a block row / column, the partial vectors added in a fixed order: no
+ * floating-point atomics, the same bits on every call.  All go by the index, use buffers of their own and leave a saved plan alone.
+ *   _maxabs     out[0] = max |x| over the blocks the index names (complex data: the modulus).  Synchronises.  A NaN among the elements gives NaN, here
+ *               and in _gershgorin, as it does in the sums.
+ *   _row_sums   out[i] = sum_j f(a_ij), f = |x| (what == 0) or |x|^2 (what == 1; any other value: -1), over the STORED blocks.  Asynchronous on stream.
+ *   _col_sums   out[j] = sum_i f(a_ij); skip_diagonal_blocks != 0: blocks on the block diagonal do not count.  Asynchronous.
+ *   _gershgorin out[0] = max_i sum_j |a_ij|.  symmetric != 0 (a stored triangle of any of the four symmetries; nblkrows == nblkcols, else -1): a stored
+ *               block off the diagonal also adds its column sums to the rows of its twin.  Composed on the device of _row_sums, _col_sums and a maximum;
+ *               synchronises once.  It sizes its vectors by the full row count, which it fetches (one more synchronisation) when a matrix' block-size
+ *               arrays and non-zero index_stamp are not among the last eight it saw; a matrix with index_stamp == 0 pays that every time.  A caller that sets
+ *               index_stamp itself must give every set of block-size arrays a stamp of its own: the same stamp at reused addresses with other
+ *               sizes would be taken for the remembered count.
+ *   _get_diag   diag[i] = a_ii from the diagonal blocks present, ZERO where a block row has no diagonal block; every one of the n elements is written.
+ *   _set_diag   a_ii = diag[i] on the diagonal blocks present; nothing else is written and no block is created (dbcsr_add_on_diag with 0 creates them).
+ *               Both: square block structure (nblkrows == nblkcols, else -1), diag has the matrix' data type; a diagonal block that is not square is
+ *               left alone (get: zeros).  Asynchronous.
+ *   _scale_by_vector  in place, side 1 (right): a_ij <- a_ij * vec[j]; side 0 (left): a_ij <- a_ij * vec[i]; any other side: -1.  vec has the matrix'
+ *               data type.  Real data: one rounding per element.  Asynchronous.
+ * n / n_out is the length of the vector: every read and write of it stays below, so a wrong length never touches memory outside the vector (elements whose
+ * entry would lie behind it are not produced / not scaled; elements of a longer out / diag behind the full length are zero). */
+int dbcsr_amd_bcsr_maxabs(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, double out[1], void* stream);
+int dbcsr_amd_bcsr_row_sums(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, int what, double* out, int64_t n_out, void* stream);
+int dbcsr_amd_bcsr_col_sums(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, int what, int skip_diagonal_blocks, double* out,
+  int64_t n_out, void* stream);
+int dbcsr_amd_bcsr_gershgorin(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, int symmetric, double out[1], void* stream);
+int dbcsr_amd_bcsr_get_diag(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, void* diag, int64_t n, void* stream);
+int dbcsr_amd_bcsr_set_diag(void* handle, libsmm_acc_data_t datatype, dbcsr_amd_bcsr* m, const void* diag, int64_t n, void* stream);
+int dbcsr_amd_bcsr_scale_by_vector(void* handle, libsmm_acc_data_t datatype, dbcsr_amd_bcsr* m, const void* vec, int64_t n, int side, void* stream);
+
 /* Measurement helper (bench.py, roofline.fabric): what the L2 <-> Infinity-Cache fabric of the current device delivers, in TB/s -- a
  * plain streaming read of a 160 MB window by all CUs, and the block gather of the block-product dataflow (4232-byte blocks from
  * pseudo-random places of the window into LDS, whole 128-byte lines counted).  Takes well under a second; synchronises the device. */

@@ -13,6 +13,18 @@ alternating:
   apply       of that, the part after the count's synchronisation (index emission + algebra_add_blocks), from the difference to a count alone
   norm        dbcsr_amd_bcsr_norm2 of A (algebra_norm2 + the final sum + one synchronisation)
   torch.norm  torch.linalg.vector_norm(a.data): the same bytes read
+  gersh.N     dbcsr_amd_bcsr_gershgorin of A without symmetry: the row sums of |x| (algebra_row_sums), the sum of the partial vectors, the maximum, one
+              synchronisation.  Yardstick: norm (the same bytes read by algebra_norm2, the same run)
+  gersh.S     the same of the stored upper triangle T of a symmetric matrix: row sums plus the column sums of the blocks off the diagonal (the per-column
+              block lists, algebra_col_sums) -- T's data is read twice.  Yardstick: norm.T, dbcsr_amd_bcsr_norm2 of T (read once)
+  colnorm     dbcsr_amd_bcsr_col_sums of |x|^2 of A (lists + algebra_col_sums + the sum of the partial vectors; asynchronous).  Yardstick: norm
+  maxabs      dbcsr_amd_bcsr_maxabs of A.  Yardstick: norm
+  scale.R/.L  dbcsr_amd_bcsr_scale_by_vector of A on the right / left with a vector of ones (A is read and written)
+  torch.mul   torch.mul(a.data, s, out=a.data) with a scalar: the same bytes through a kernel that is not ours, the yardstick of scale.R / scale.L
+
+With --colsums (lab build: DBCSR_AMD_LAB=1) only this is timed, alternating: norm, and dbcsr_amd_bcsr_col_sums of |x|^2 of A through an engine per form of
+algebra_col_sums (DBCSR_AMD_ALG_COLSUMS; csrc/mm_algebra.h): col.0 what ships, col.1 staging without the per-lane add loop, col.2 loads added in registers
+without LDS, col.3 no block walked (list build, launch, sum of the partial vectors), col.4 the lane-per-column form without staging; col.lists is col.3.
 
 A sample is `--reps` calls back to back between two device events, divided by reps.  Bytes are counted from the shapes: 8 * (elements read + elements
 written) of the data areas, index arrays left out.  Spread = (max - min) / median over the samples."""
@@ -53,6 +65,46 @@ def sample(fn, reps):
     return e0.elapsed_time(e1) / reps
 
 
+def colsums(args, say, lines, rng, b, nb, st):
+    assert L.want_lab(), "--colsums needs the lab build (DBCSR_AMD_LAB=1)"
+    A = matrix_of(rng.random((nb, nb)) < args.fill_flat, b, 1)
+    a = A.desc()
+    f64 = L.dbcsr_type_real_8
+    out2 = (C.c_double * 2)()
+    colv = torch.empty(nb * b, dtype=torch.float64, device="cuda")
+    engines = {}
+    for v in range(5):
+        os.environ["DBCSR_AMD_ALG_COLSUMS"] = str(v)
+        engines[v] = MultiplyEngine(lab=True)
+    del os.environ["DBCSR_AMD_ALG_COLSUMS"]
+    check = lambda rc: rc == 0 or sys.exit("a library call failed (%d)" % rc)
+    run = {"norm": lambda: check(engines[0].L.dbcsr_amd_bcsr_norm2(engines[0].h, f64, C.byref(a), 0, out2, st.ptr))}
+    for v in range(5):
+        run["col.%d" % v] = (lambda e: lambda: check(e.L.dbcsr_amd_bcsr_col_sums(e.h, f64, C.byref(a), 1, 0, colv.data_ptr(), colv.numel(), st.ptr)))(engines[v])
+    check(engines[0].L.dbcsr_amd_bcsr_col_sums(engines[0].h, f64, C.byref(a), 1, 0, colv.data_ptr(), colv.numel(), st.ptr))
+    ref = colv.clone()
+    check(engines[4].L.dbcsr_amd_bcsr_col_sums(engines[4].h, f64, C.byref(a), 1, 0, colv.data_ptr(), colv.numel(), st.ptr))
+    torch.cuda.synchronize()
+    say("col.4 against col.0: largest relative difference of a column sum %.2e" % float(((colv - ref).abs() / ref).max()))
+    times = {k: [] for k in run}
+    for step in range(args.warmup + args.alternations):
+        for k in run:
+            t = sample(run[k], args.reps)
+            if step >= args.warmup:
+                times[k].append(t)
+    say("")
+    say("forms of algebra_col_sums, %d blocks, %.1f MB" % (A.nblks, 8e-6 * A.nze))
+    med = {}
+    for k in run:
+        v = sorted(times[k])
+        med[k] = v[len(v) // 2]
+        say("  %-6s  median %8.4f ms  min %8.4f  max %8.4f  spread %5.1f %%  %.2f of norm   samples: %s"
+            % (k, med[k], v[0], v[-1], 100 * (v[-1] - v[0]) / med[k], med[k] / med["norm"], " ".join("%.4f" % x for x in times[k])))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=32768)
@@ -62,6 +114,7 @@ def main():
     ap.add_argument("--alternations", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--colsums", action="store_true", help="the forms of algebra_col_sums against each other (lab build)")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "ops_bench.py measures on the GPU"
@@ -73,6 +126,8 @@ def main():
     say("%d alternations after %d warm-up rounds, %d calls per sample; ms per call; GB/s = 8 * (elements read + written) / time" % (args.alternations, args.warmup, args.reps))
     E, st = MultiplyEngine(), StreamHandle()
     rng = np.random.default_rng(2)
+    if args.colsums:
+        return colsums(args, say, lines, rng, b, nb, st)
     # the same-pattern pair
     mask = rng.random((nb, nb)) < args.fill_flat
     A, B = matrix_of(mask, b, 1), matrix_of(mask, b, 2)
@@ -99,6 +154,14 @@ def main():
     nblk_s, nze_s, same_s = C.c_int64(), C.c_int64(), C.c_int32()
     count_same = lambda: E.L.dbcsr_amd_bcsr_add_count(E.h, C.byref(a), C.byref(b_), 0, row_p_same.data_ptr(), C.byref(nblk_s), C.byref(nze_s), C.byref(same_s), st.ptr)
 
+    # norms and vectors: A (full), the stored upper triangle T of a symmetric matrix of the same shape
+    T = matrix_of(np.triu(mask), b, 5)
+    t_ = T.desc()
+    f64 = L.dbcsr_type_real_8
+    ones = torch.ones(nb * b, dtype=torch.float64, device="cuda")
+    colv = torch.empty(nb * b, dtype=torch.float64, device="cuda")
+    check = lambda rc: rc == 0 or sys.exit("a library call failed (%d)" % rc)
+
     def general():
         assert count() == 0
         assert E.L.dbcsr_amd_bcsr_add_apply(E.h, L.dbcsr_type_real_8, one, C.byref(ga), two, C.byref(gb), C.byref(gd), st.ptr) == 0
@@ -114,8 +177,18 @@ def main():
         "count": lambda: count(),
         "norm": lambda: E.L.dbcsr_amd_bcsr_norm2(E.h, L.dbcsr_type_real_8, C.byref(a), 0, out2, st.ptr),
         "torch.norm": lambda: torch.linalg.vector_norm(A.data),
+        "gersh.N": lambda: check(E.L.dbcsr_amd_bcsr_gershgorin(E.h, f64, C.byref(a), 0, out2, st.ptr)),
+        "norm.T": lambda: check(E.L.dbcsr_amd_bcsr_norm2(E.h, f64, C.byref(t_), 1, out2, st.ptr)),
+        "gersh.S": lambda: check(E.L.dbcsr_amd_bcsr_gershgorin(E.h, f64, C.byref(t_), 1, out2, st.ptr)),
+        "colnorm": lambda: check(E.L.dbcsr_amd_bcsr_col_sums(E.h, f64, C.byref(a), 1, 0, colv.data_ptr(), colv.numel(), st.ptr)),
+        "maxabs": lambda: check(E.L.dbcsr_amd_bcsr_maxabs(E.h, f64, C.byref(a), out2, st.ptr)),
+        "scale.R": lambda: check(E.L.dbcsr_amd_bcsr_scale_by_vector(E.h, f64, C.byref(a), ones.data_ptr(), ones.numel(), 1, st.ptr)),
+        "scale.L": lambda: check(E.L.dbcsr_amd_bcsr_scale_by_vector(E.h, f64, C.byref(a), ones.data_ptr(), ones.numel(), 0, st.ptr)),
+        "torch.mul": lambda: torch.mul(A.data, 1.0, out=A.data),
     }
-    nbytes = {"flat": 24 * A.nze, "torch.add": 24 * A.nze, "flat.count": 0, "general": 8 * (GA.nze + GB.nze + nze.value), "count": 0, "norm": 8 * A.nze, "torch.norm": 8 * A.nze}
+    nbytes = {"flat": 24 * A.nze, "torch.add": 24 * A.nze, "flat.count": 0, "general": 8 * (GA.nze + GB.nze + nze.value), "count": 0, "norm": 8 * A.nze, "torch.norm": 8 * A.nze,
+              "gersh.N": 8 * A.nze, "norm.T": 8 * T.nze, "gersh.S": 16 * T.nze, "colnorm": 8 * A.nze, "maxabs": 8 * A.nze, "scale.R": 16 * A.nze, "scale.L": 16 * A.nze,
+              "torch.mul": 16 * A.nze}
     times = {k: [] for k in run}
     for step in range(args.warmup + args.alternations):
         for k in run:
@@ -139,6 +212,11 @@ def main():
     flat_rate, torch_rate = nbytes["flat"] / med["flat"], nbytes["torch.add"] / med["torch.add"]
     say("  flat against torch.add: %.2f of its rate; general (count + apply) against torch.add: %.2f; apply alone: %.2f; norm against torch.norm: %.2f"
         % (flat_rate / torch_rate, nbytes["general"] / med["general"] / torch_rate, nbytes["general"] / apply_ms / torch_rate, med["torch.norm"] / med["norm"]))
+    say("")
+    say("norms and vectors: time against the yardstick of the same run (median / median; spread of the ratio over the alternations, sample by sample)")
+    for k, y in (("gersh.N", "norm"), ("colnorm", "norm"), ("maxabs", "norm"), ("gersh.S", "norm.T"), ("scale.R", "torch.mul"), ("scale.L", "torch.mul")):
+        r = sorted(x / z for x, z in zip(times[k], times[y]))
+        say("  %-8s / %-9s  %.2f   (per alternation %.2f ... %.2f)" % (k, y, med[k] / med[y], r[0], r[-1]))
     if args.out:
         with open(args.out, "w") as f:
             f.write("\n".join(lines) + "\n")
