@@ -800,5 +800,269 @@ algebra_scale_by_vector(const int* __restrict__ row_p, const int* __restrict__ c
   }
 }
 
+// ---- matrix-vector product (y <- alpha op(A) x + beta y) -----------------------------------------------------------------------------------------------
+// The two passes above with the term g(a_e) x[...] in place of f(a_e) (g: identity or conjugate): algebra_matvec_rows is algebra_row_sums' walk with
+// x taken per element COLUMN, algebra_matvec_cols is algebra_col_sums' with x taken per element ROW.  Sums are carried in double / complex double
+// (MatvecAcc), one partial vector per wave of a block row / column; algebra_matvec_combine adds the partial vectors of both passes in a fixed order and
+// applies alpha and beta.  Every read of x stays below n_x (a term whose entry of x would lie behind it is not formed), every write of y below n_y.
+template <typename T> struct MatvecAcc { using type = double; };
+template <> struct MatvecAcc<z64> { using type = z64; };
+
+__device__ __forceinline__ double matvec_term(double a, double x, int) { return a * x; }
+__device__ __forceinline__ double matvec_term(float a, float x, int) { return (double)a * (double)x; }   // (exact in double)
+__device__ __forceinline__ z64 matvec_term(z64 a, z64 x, int conj) { return z64(a.re, conj ? -a.im : a.im) * x; }
+
+// Row pass, the elements of one block through the lanes of a wave: the slots of row_sum_slots.  xc = x at the block column's first element, nx the number
+// of entries x has from there.  Slot s starts at element e0 = V s - A = i + m j of the column-major block; a lane's stride V P is a multiple of m, so from
+// one slot to the next i stays and j grows by q = V P / m: one division per block and lane.  x is read straight from global memory: a wave's 16-byte loads
+// cover V P consecutive elements, that is q (23 x 23 doubles: 4) consecutive entries of x, one cache line that stays in L1 / L2 (x is small next to A) --
+// and an entry is loaded again only where a slot crosses into the next column.
+template <typename T, int A>
+__device__ __forceinline__ void matvec_row_slots(const T* __restrict__ d, int ne, int m, int lane, int P, int vec_ok, int conj, const T* __restrict__ xc,
+                                                 int64_t nx, typename MatvecAcc<T>::type (&acc)[2 * Pack16<T>::V - 1]) {
+  constexpr int V = Pack16<T>::V;
+  const int nslots = (ne + A + V - 1) / V, q = V * P / m;
+  int e0 = V * lane - A;
+  int j = e0 >= 0 ? e0 / m : -((-e0 + m - 1) / m);   // (floor: the slot in front of the block's first element)
+  const int i = e0 - j * m;
+  for (int s = lane; s < nslots; s += P, e0 += V * P, j += q) {
+    int iu = i, ju = j;
+    bool ok = ju >= 0 && ju < nx;
+    T xv = ok ? xc[ju] : T(0);
+    auto next = [&]() {
+      if (++iu == m) {
+        iu = 0, ++ju;
+        ok = ju >= 0 && ju < nx;
+        xv = ok ? xc[ju] : T(0);
+      }
+    };
+    if (vec_ok && e0 >= 0 && e0 + V <= ne) {
+      const Pack16<T> a = *reinterpret_cast<const Pack16<T>*>(d + e0);
+#pragma unroll
+      for (int u = 0; u < V; ++u) {
+        if (ok) acc[V - 1 - A + u] = acc[V - 1 - A + u] + matvec_term(a.v[u], xv, conj);
+        if (u + 1 < V) next();
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < V; ++u) {
+        if (e0 + u >= 0 && e0 + u < ne && ok) acc[V - 1 - A + u] = acc[V - 1 - A + u] + matvec_term(d[e0 + u], xv, conj);
+        if (u + 1 < V) next();
+      }
+    }
+  }
+}
+
+// partials[sub * n_y + yoff[row] + r] = sum over the blocks sub, sub + S, ... of block row `row` of sum_j g(a_rj) x[xoff[c] + j], for every element row r of
+// the block row (zero when the wave met no block): algebra_row_sums with another term.  skip_diag: blocks on the block diagonal do not count (the twin part
+// of the transposed product of a stored triangle).
+template <typename T>
+__global__ void __launch_bounds__(256)
+algebra_matvec_rows(const int* __restrict__ row_p, const int* __restrict__ col_i, const int64_t* __restrict__ blk_p, const T* __restrict__ data,
+                    const int* __restrict__ rs, const int* __restrict__ cs, const int64_t* __restrict__ yoff, const int64_t* __restrict__ xoff, int nbr, int S,
+                    int conj, int skip_diag, int vec_ok, const T* __restrict__ x, int64_t n_x, int64_t n_y,
+                    typename MatvecAcc<T>::type* __restrict__ partials) {
+  using Acc = typename MatvecAcc<T>::type;
+  constexpr int V = Pack16<T>::V, K = 2 * V - 1;
+  __shared__ Acc red[4][K * 64];
+  const int lane = threadIdx.x & 63;
+  const int64_t wv = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int row = (int)(wv / S), sub = (int)(wv % S);
+  if (row >= nbr) return;
+  const int m = rs[row];
+  if (m <= 0) return;
+  const int64_t base = yoff[row];
+  Acc* __restrict__ mine = partials + (size_t)sub * n_y;
+  const int b0 = row_p[row] + sub, b1 = row_p[row + 1];
+  const int g = V == 1 ? 1 : (m % V == 0 ? V : (m % 2 == 0 ? 2 : 1));   // gcd(V, m), V = 1, 2 or 4
+  const int p = m / g;
+  if (p > 64) {
+    for (int r0 = 0; r0 < m; r0 += 64) {
+      const int r = r0 + lane;
+      Acc acc = Acc(0.0);
+      if (r < m)
+        for (int b = b0; b < b1; b += S) {
+          const int c = col_i[b];
+          if (skip_diag && c == row) continue;
+          const int n = cs[c];
+          const T* d = data + blk_p[b] + r;
+          const int64_t xb = xoff[c];
+          for (int j = 0; j < n; ++j)
+            if (xb + j < n_x) acc = acc + matvec_term(d[(size_t)m * j], x[xb + j], conj);
+        }
+      if (r < m && base + r < n_y) mine[base + r] = acc;
+    }
+    return;
+  }
+  const int P = (64 / p) * p;
+  Acc acc[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) acc[k] = Acc(0.0);
+  if (lane < P)
+    for (int b = b0; b < b1; b += S) {
+      const int c = col_i[b];
+      if (skip_diag && c == row) continue;   // (wave-uniform)
+      const int ne = m * cs[c];
+      const int64_t off = blk_p[b], xb = xoff[c];
+      const T* d = data + off;
+      const T* xc = x + xb;
+      const int64_t nx = n_x - xb;
+      const int a = vec_ok ? (int)(off & (V - 1)) : 0;   // (wave-uniform)
+      if (V == 1 || a == 0) matvec_row_slots<T, 0>(d, ne, m, lane, P, vec_ok, conj, xc, nx, acc);
+      else if (a == 1) matvec_row_slots<T, 1 % V>(d, ne, m, lane, P, vec_ok, conj, xc, nx, acc);
+      else if (a == 2) matvec_row_slots<T, 2 % V>(d, ne, m, lane, P, vec_ok, conj, xc, nx, acc);
+      else matvec_row_slots<T, 3 % V>(d, ne, m, lane, P, vec_ok, conj, xc, nx, acc);
+    }
+  Acc* slice = red[threadIdx.x >> 6];
+#pragma unroll
+  for (int k = 0; k < K; ++k) slice[k * 64 + lane] = acc[k];
+  wave_lds_handover();   // (the slice is this wave's alone)
+  for (int r = lane; r < m; r += 64) {
+    Acc sum = Acc(0.0);
+    for (int k = 0; k < K; ++k) {
+      // the lanes l with (V l + k - (V - 1)) mod m == r, as in algebra_row_sums
+      int cur = ((k - (V - 1)) % m + m) % m, l0 = 0;
+      while (l0 < p && cur != r) {
+        ++l0;
+        cur += V;
+        if (cur >= m) cur -= m;
+        if (cur >= m) cur %= m;   // (m < V)
+      }
+      if (l0 < p)
+        for (int l = l0; l < P; l += p) sum = sum + slice[k * 64 + l];
+    }
+    if (base + r < n_y) mine[base + r] = sum;
+  }
+}
+
+// elements of a staged piece: a workgroup's four slices stay within the 32 KB of kStageElems doubles per wave (a complex term is two doubles)
+template <typename T>
+constexpr int kMatvecPiece = kStageElems * (int)sizeof(double) / (int)sizeof(typename MatvecAcc<T>::type);
+
+// len <= kMatvecPiece elements at d (element `off` of a 16-byte aligned area; element `first` of a part of a column-major block that starts with a whole
+// column of m elements) -> g(a_e) x[row of e] of them in lds[0 ... len), with aligned 16-byte loads where vec_ok: stage_absval with another term.  xr = x
+// at the block row's first element, nx the number of entries x has from there (zero is staged for a term that is not formed)
+template <typename T>
+__device__ __forceinline__ void stage_matvec(const T* __restrict__ d, int64_t off, int len, int first, int m, int lane, int vec_ok, int conj,
+                                             const T* __restrict__ xr, int64_t nx, typename MatvecAcc<T>::type* lds) {
+  using Acc = typename MatvecAcc<T>::type;
+  constexpr int V = Pack16<T>::V;
+  auto one = [&](int e) {
+    const int i = (first + e) % m;
+    lds[e] = i < nx ? matvec_term(d[e], xr[i], conj) : Acc(0.0);
+  };
+  if (V > 1 && vec_ok) {
+    const int h = head_of<T>(off), head = h < len ? h : len, nv = (len - head) / V, done = head + nv * V;
+    if (lane < head) one(lane);
+    const Pack16<T>* dv = reinterpret_cast<const Pack16<T>*>(d + head);
+    for (int q = lane; q < nv; q += 64) {
+      const Pack16<T> a = dv[q];
+      const int e = head + q * V;
+      int i = (first + e) % m;
+#pragma unroll
+      for (int u = 0; u < V; ++u) {
+        lds[e + u] = i < nx ? matvec_term(a.v[u], xr[i], conj) : Acc(0.0);
+        if (++i == m) i = 0;
+      }
+    }
+    if (done + lane < len) one(done + lane);
+  } else {
+    for (int e = lane; e < len; e += 64) one(e);
+  }
+}
+
+// partials[sub * n_y + yoff[c] + j] = sum over the entries sub, sub + S, ... of block column c's list of sum_i g(a_ij) x[xoff[r] + i]: the staged form of
+// algebra_col_sums with another term (lane j owns column j, 64 columns at a time; a piece is staged in the wave's LDS slice and lane j adds what the piece
+// holds of its run in the rotated, fixed order).  skip_diag: blocks on the block diagonal do not count (the twin part of the product of a stored triangle).
+template <typename T>
+__global__ void __launch_bounds__(256)
+algebra_matvec_cols(const int* __restrict__ col_p, const int* __restrict__ list, const int64_t* __restrict__ blk_p, const T* __restrict__ data,
+                    const int* __restrict__ rs, const int* __restrict__ cs, const int64_t* __restrict__ yoff, const int64_t* __restrict__ xoff, int nbc, int S,
+                    int conj, int skip_diag, int vec_ok, const T* __restrict__ x, int64_t n_x, int64_t n_y,
+                    typename MatvecAcc<T>::type* __restrict__ partials) {
+  using Acc = typename MatvecAcc<T>::type;
+  constexpr int kPiece = kMatvecPiece<T>;
+  __shared__ Acc stage[4][kPiece];
+  const int lane = threadIdx.x & 63;
+  const int64_t wv = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int c = (int)(wv / S), sub = (int)(wv % S);
+  if (c >= nbc) return;
+  const int n = cs[c];
+  const int64_t base = yoff[c];
+  Acc* __restrict__ mine = partials + (size_t)sub * n_y;
+  Acc* lds = stage[threadIdx.x >> 6];
+  for (int j0 = 0; j0 < n; j0 += 64) {
+    const int nj = n - j0 < 64 ? n - j0 : 64;
+    Acc acc = Acc(0.0);
+    for (int t = col_p[c] + sub; t < col_p[c + 1]; t += S) {
+      const int r = list[2 * (size_t)t + 1];
+      if (skip_diag && r == c) continue;
+      const int m = rs[r];
+      if (m <= 0) continue;
+      const int64_t off = blk_p[list[2 * (size_t)t]] + (int64_t)j0 * m, xb = xoff[r];
+      const int total = nj * m, run0 = lane * m;   // the part of the block with this pass' columns; lane's run inside it
+      for (int c0 = 0; c0 < total; c0 += kPiece) {
+        const int len = total - c0 < kPiece ? total - c0 : kPiece;
+        stage_matvec(data + off + c0, off + c0, len, c0, m, lane, vec_ok, conj, x + xb, n_x - xb, lds);
+        wave_lds_handover();   // (the slice is this wave's alone)
+        const int lo = run0 > c0 ? run0 : c0, hi = run0 + m < c0 + len ? run0 + m : c0 + len;
+        if (lane < nj && lo < hi) {
+          const int cnt = hi - lo;
+          const Acc* run = lds + (lo - c0);
+          int i = lane % cnt;
+          for (int k = 0; k < cnt; ++k) {
+            acc = acc + run[i];
+            if (++i == cnt) i = 0;
+          }
+        }
+        wave_lds_handover();   // (the next piece overwrites the slice)
+      }
+    }
+    if (lane < nj && base + j0 + lane < n_y) mine[base + j0 + lane] = acc;
+  }
+}
+
+// beta * y in the data's own precision, every operation rounded on its own: what alpha == 0 leaves of the product.  (The library is compiled with
+// contraction into fused multiply-adds allowed; the pragma takes it from the complex product, whose bits would otherwise depend on the compiler.)
+__device__ __forceinline__ double matvec_scaled(double b, double y) { return b * y; }
+__device__ __forceinline__ float matvec_scaled(float b, float y) { return b * y; }
+__device__ __forceinline__ z64 matvec_scaled(z64 b, z64 y) {
+#pragma clang fp contract(off)
+  const double rr = b.re * y.re, ii = b.im * y.im, ri = b.re * y.im, ir = b.im * y.re;
+  return z64(rr - ii, ri + ir);
+}
+__device__ __forceinline__ double matvec_signed(double v, double sign) { return sign * v; }
+__device__ __forceinline__ z64 matvec_signed(z64 v, double sign) { return z64(sign * v.re, sign * v.im); }
+__device__ __forceinline__ double matvec_wide(double v) { return v; }
+__device__ __forceinline__ double matvec_wide(float v) { return (double)v; }
+__device__ __forceinline__ z64 matvec_wide(z64 v) { return v; }
+template <typename T> __device__ __forceinline__ T matvec_narrow(typename MatvecAcc<T>::type v) { return (T)v; }
+template <> __device__ __forceinline__ z64 matvec_narrow<z64>(z64 v) { return v; }
+
+// bits of `mode`: alpha == 0 (no pass ran: y <- beta y in the data's precision, S_r = S_c = 0), beta == 0 (y is not read)
+constexpr int kMatvecNoProduct = 1, kMatvecBetaZero = 2;
+
+// y[i] = alpha (row_sign * sum_k row partial k + col_sign * sum_k column partial k) + beta y[i] for i below n_y and below *total (the full length, on the
+// device): the partial vectors in the order rows 0 ... S_r - 1, then columns 0 ... S_c - 1 (the column partials lie behind the row partials; a sign of +-1 is
+// exact), alpha and beta applied in double, one rounding to the data's type.  Nothing else is written.
+template <typename T>
+__global__ void __launch_bounds__(256)
+algebra_matvec_combine(const typename MatvecAcc<T>::type* __restrict__ partials, int S_r, int S_c, double row_sign, double col_sign, int64_t n_y,
+                       const int64_t* __restrict__ total, typename MatvecAcc<T>::type alpha, typename MatvecAcc<T>::type beta, int mode, T* __restrict__ y) {
+  using Acc = typename MatvecAcc<T>::type;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_y || i >= *total) return;
+  if (mode & kMatvecNoProduct) {
+    y[i] = (mode & kMatvecBetaZero) ? T(0) : matvec_scaled(matvec_narrow<T>(beta), y[i]);
+    return;
+  }
+  Acc s = Acc(0.0);
+  for (int k = 0; k < S_r; ++k) s = s + matvec_signed(partials[(size_t)k * n_y + i], row_sign);
+  for (int k = 0; k < S_c; ++k) s = s + matvec_signed(partials[(size_t)(S_r + k) * n_y + i], col_sign);
+  Acc r = alpha * s;
+  if (!(mode & kMatvecBetaZero)) r = r + beta * matvec_wide(y[i]);
+  y[i] = matvec_narrow<T>(r);
+}
+
 }  // namespace dbcsr_amd
 #endif

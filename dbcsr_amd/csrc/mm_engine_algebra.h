@@ -1,7 +1,7 @@
 // mm_engine_algebra.h -- part of mm_engine.hip (included inside extern "C", after mm_engine_ops.h): the C-ABI operations between multiplies --
 // dbcsr_amd_bcsr_add_count / _add_apply, the pieces of dbcsr_add_on_diag (dbcsr_amd_bcsr_diag_count / _diag_fill / _diag_shift), dbcsr_amd_bcsr_trace,
-// _dot, _norm2, and the norms and vectors: dbcsr_amd_bcsr_maxabs, _row_sums, _col_sums, _gershgorin, _get_diag, _set_diag, _scale_by_vector.  Kernels:
-// mm_algebra.h.  The reductions, the diagonal pieces, the same-pattern add and the norms and vectors use buffers of their own (Engine::alg_*) and the
+// _dot, _norm2, and the norms and vectors: dbcsr_amd_bcsr_maxabs, _row_sums, _col_sums, _gershgorin, _get_diag, _set_diag, _scale_by_vector, _matvec.
+// Kernels: mm_algebra.h.  The reductions, the diagonal pieces, the same-pattern add and the norms and vectors use buffers of their own (Engine::alg_*) and the
 // scan's scratch, which no saved plan depends on (the checksum uses it the same way): they do NOT invalidate the plan.  The union add borrows the
 // symbolic phase's bitmaps and prefix arrays and invalidates it, as filter and crop do.
 #ifndef DBCSR_AMD_MM_ENGINE_ALGEBRA_H
@@ -536,6 +536,82 @@ int dbcsr_amd_bcsr_scale_by_vector(void* handle, libsmm_acc_data_t datatype, dbc
   if (vector_offsets(E, st, m, &roff, &coff)) return -1;
   DBCSR_AMD_BY_TYPE(scale_by_vector_launch, st, m, side ? coff : roff, side, vec, n);
   return check(hipGetLastError(), "dbcsr_amd_bcsr_scale_by_vector", __FILE__, __LINE__);
+}
+// ---- matrix-vector product ---------------------------------------------------------------------------------------------------------------------------
+extern "C++" {
+// one pass over the stored blocks: by block row (y per row of A, x per column) or by block column (y per column of A, x per row)
+struct MatvecPass {
+  int on, skip_diag, conj;
+  double sign;
+};
+
+// The passes of y <- op(F) x, F the matrix the index stands for.  No symmetry (kind -1): F = A, one pass.  A stored triangle (kind = bit 0 negates, bit 1
+// conjugates the twin: S 0, A 1, H 2, K 3; g = conjugate with bit 1, s = -1 with bit 0): block (r, c), r != c, stands for F_rc = a and F_cr = s g(a)^T,
+// a diagonal block for itself.
+//            rows: y_r += ... x_c                   cols: y_c += ... x_r
+//   op N     a            every block               s g(a)^T     off the diagonal
+//   op T     s g(a)       off the diagonal          a^T          every block
+//   op C     s conj g(a)  off the diagonal          conj(a)^T    every block
+static void matvec_passes(int kind, char op, MatvecPass* rows, MatvecPass* cols) {
+  const int g = kind >= 0 ? (kind >> 1) & 1 : 0;
+  const double s = kind >= 0 && (kind & 1) ? -1.0 : 1.0;
+  const MatvecPass off = {0, 0, 0, 1.0};
+  if (op == 'N') {
+    *rows = MatvecPass{1, 0, 0, 1.0};
+    *cols = kind >= 0 ? MatvecPass{1, 1, g, s} : off;
+  } else {
+    const int c = op == 'C' ? 1 : 0;
+    *cols = MatvecPass{1, 0, c, 1.0};
+    *rows = kind >= 0 ? MatvecPass{1, 1, g ^ c, s} : off;
+  }
+}
+
+// (the caller made alg_sums hold (S_r + S_c) n_y sums, the column list when the column pass is on, and the offsets)
+template <typename T>
+static void matvec_launch(Engine* E, hipStream_t st, const dbcsr_amd_bcsr* a, const MatvecPass& rp, const MatvecPass& cp, int S_r, int S_c,
+                          const int64_t* roff, const int64_t* coff, const int64_t* total, const double alpha[2], const double beta[2], int mode,
+                          const void* x, int64_t n_x, void* y, int64_t n_y) {
+  using Acc = typename MatvecAcc<T>::type;
+  Acc* sums = reinterpret_cast<Acc*>(E->alg_sums.p);
+  const int nbr = a->nblkrows, nbc = a->nblkcols, vec_ok = aligned16(a->data);
+  if (S_r > 0)
+    hipLaunchKernelGGL((algebra_matvec_rows<T>), grid_for((int64_t)nbr * S_r * 64), dim3(256), 0, st, a->row_p, a->col_i, a->blk_p,
+                       static_cast<const T*>(a->data), a->row_blk_size, a->col_blk_size, roff, coff, nbr, S_r, rp.conj, rp.skip_diag, vec_ok,
+                       static_cast<const T*>(x), n_x, n_y, sums);
+  if (S_c > 0)
+    hipLaunchKernelGGL((algebra_matvec_cols<T>), grid_for((int64_t)nbc * S_c * 64), dim3(256), 0, st, E->alg_col_p.p, E->alg_list.p, a->blk_p,
+                       static_cast<const T*>(a->data), a->row_blk_size, a->col_blk_size, coff, roff, nbc, S_c, cp.conj, cp.skip_diag, vec_ok,
+                       static_cast<const T*>(x), n_x, n_y, sums + (size_t)S_r * n_y);
+  hipLaunchKernelGGL((algebra_matvec_combine<T>), grid_for(n_y), dim3(256), 0, st, sums, S_r, S_c, rp.sign, cp.sign, n_y, total,
+                     algebra_scalar<Acc>(alpha), algebra_scalar<Acc>(beta), mode, static_cast<T*>(y));
+}
+}  // extern "C++"
+
+int dbcsr_amd_bcsr_matvec(void* handle, libsmm_acc_data_t datatype, char trans, const double alpha[2], const dbcsr_amd_bcsr* a, int kind, const void* x,
+                          int64_t n_x, const double beta[2], void* y, int64_t n_y, void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E || !alpha || !a || !beta || n_x < 0 || n_y < 0 || (n_x > 0 && !x) || (n_y > 0 && !y)) return -1;
+  if (trans != 'N' && trans != 'T' && trans != 'C') return -1;
+  if (kind < -1 || kind > 3 || (kind >= 0 && a->nblkrows != a->nblkcols)) return -1;
+  if (!algebra_type(datatype)) return -10;
+  const size_t esize = datatype == dbcsr_type_real_8 ? 8 : datatype == dbcsr_type_real_4 ? 4 : 16;
+  const uintptr_t x0 = reinterpret_cast<uintptr_t>(x), y0 = reinterpret_cast<uintptr_t>(y);
+  if (n_x > 0 && n_y > 0 && x0 < y0 + esize * (size_t)n_y && y0 < x0 + esize * (size_t)n_x) return -1;   // x and y must not overlap
+  hipStream_t st = stream_of(stream);
+  if (n_y == 0 || a->nblkrows == 0 || a->nblkcols == 0) return 0;   // (no full row: nothing to write)
+  const bool zc = datatype == dbcsr_type_complex_8;
+  const bool alpha_zero = alpha[0] == 0.0 && (!zc || alpha[1] == 0.0), beta_zero = beta[0] == 0.0 && (!zc || beta[1] == 0.0);
+  const bool product = !alpha_zero && a->nblks > 0;   // alpha == 0: A and x are not read; an empty matrix: y <- beta y
+  const int mode = (product ? 0 : kMatvecNoProduct) | (beta_zero ? kMatvecBetaZero : 0);
+  MatvecPass rp = {0, 0, 0, 1.0}, cp = rp;
+  if (product) matvec_passes(kind, trans, &rp, &cp);
+  const int S_r = rp.on ? row_split(a->nblkrows, a->nblks) : 0, S_c = cp.on ? row_split(a->nblkcols, a->nblks) : 0;
+  const int64_t *roff = nullptr, *coff = nullptr;
+  if (E->alg_sums.ensure((size_t)(S_r + S_c) * (size_t)n_y * (zc ? 2 : 1) + 2) || vector_offsets(E, st, a, &roff, &coff)) return -1;
+  if (cp.on && col_list_build(E, st, a)) return -1;
+  const int64_t* total = trans == 'N' ? roff + a->nblkrows : coff + a->nblkcols;   // the full rows of op(A)
+  DBCSR_AMD_BY_TYPE(matvec_launch, E, st, a, rp, cp, S_r, S_c, roff, coff, total, alpha, beta, mode, x, n_x, y, n_y);
+  return check(hipGetLastError(), "dbcsr_amd_bcsr_matvec", __FILE__, __LINE__);
 }
 #undef DBCSR_AMD_BY_TYPE
 

@@ -12,6 +12,7 @@
     dbcsr_norm(matrix, which_norm, norm_vector)                 one of the three, or the column norms sqrt(sum_i |a_ij|^2)
     dbcsr_get_diag(matrix) / dbcsr_set_diag(matrix, diag)       the diagonal as a device vector
     dbcsr_scale_by_vector(matrix, alpha, side)                  A <- A*diag(alpha) ("right") or diag(alpha)*A ("left")
+    dbcsr_matvec(matrix, vec_in, vec_out, alpha, beta, trans)   y <- alpha*op(A)*x + beta*y with dense device vectors (not a mirror, see there)
 
 Same argument names and error behaviour; the work is done by the C-ABI engine (include/dbcsr_amd_mm.h, "Matrix algebra between
 multiplies") on the GPU, for float64, float32 and complex128 data.  One rank / one device here: of a distributed matrix trace, dot
@@ -351,3 +352,46 @@ def dbcsr_scale_by_vector(matrix, alpha, side, engine=None, stream=None):
     rc = E.L.dbcsr_amd_bcsr_scale_by_vector(E.h, matrix.dtype_code, C.byref(d), alpha.data_ptr() if n else None, n, 1 if side == "right" else 0, st.ptr)
     if rc != 0:
         raise RuntimeError("dbcsr_amd_bcsr_scale_by_vector failed (%d)" % rc)
+
+
+def dbcsr_matvec(matrix, vec_in, vec_out=None, alpha=1.0, beta=0.0, trans="N", engine=None, stream=None):
+    """vec_out <- alpha * op(A) * vec_in + beta * vec_out with dense device vectors of the matrix' data type: what a Lanczos, Arnoldi or power step, a
+    residual or the application of a preconditioner needs.  NOT a mirror of a routine of the reference: the reference keeps its vectors as one-column
+    DBCSR matrices (dbcsr_matrix_colvec_multiply), and its signature could not be checked against its sources -- so this name does not claim to be it.
+    trans: 'N', 'T' or 'C' (conjugate transpose; real data: 'T').  vec_in has one element per full column of op(A), vec_out one per full row, in the
+    order of the dense matrix (as dbcsr_get_diag).  With symmetry 'S' / 'A' (real data) or 'H' / 'K' (complex data) the matrix is a stored triangle
+    with a square structure and the product is that of the desymmetrized matrix.  beta == 0: vec_out is not read (a NaN in it does not reach the
+    result); alpha == 0: the matrix and vec_in are not read.  vec_out=None (then beta must be 0) allocates the result on the matrix' device and stream.
+    The vectors must not overlap.  Asynchronous on the stream; returns vec_out."""
+    sym = _check_symmetry("dbcsr_matvec", matrix)
+    if trans not in ("N", "T", "C"):
+        raise ValueError("dbcsr_matvec: trans must be 'N', 'T' or 'C', got %r" % (trans,))
+    matrix.dtype_code
+    kind = -1
+    if sym != "N":
+        kind = matrix.symmetry_kind()
+        _check_square("dbcsr_matvec", matrix)
+    _check_scalar("dbcsr_matvec", matrix, alpha, beta)
+    n_rows, n_cols = _full_size(matrix.row_blk_size), _full_size(matrix.col_blk_size)
+    n_x, n_y = (n_cols, n_rows) if trans == "N" else (n_rows, n_cols)
+    _check_vector("dbcsr_matvec", matrix, vec_in, n_x)
+    if vec_out is None:
+        if beta != 0:
+            raise ValueError("dbcsr_matvec: beta != 0 needs a vec_out")
+    else:
+        _check_vector("dbcsr_matvec", matrix, vec_out, n_y)
+        size = vec_in.element_size()
+        x0, y0 = vec_in.data_ptr(), vec_out.data_ptr()
+        if n_x and n_y and x0 < y0 + size * n_y and y0 < x0 + size * n_x:
+            raise ValueError("dbcsr_matvec: vec_in and vec_out overlap")
+    E = engine or default_engine()
+    st = StreamHandle(stream)
+    if vec_out is None:
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            vec_out = torch.empty(n_y, dtype=matrix.dtype, device=matrix.row_p.device)
+    d = matrix.desc()
+    rc = E.L.dbcsr_amd_bcsr_matvec(E.h, matrix.dtype_code, trans.encode(), _z(alpha), C.byref(d), kind, vec_in.data_ptr() if n_x else None, n_x,
+                                   _z(beta), vec_out.data_ptr() if n_y else None, n_y, st.ptr)
+    if rc != 0:
+        raise RuntimeError("dbcsr_amd_bcsr_matvec failed (%d)" % rc)
+    return vec_out

@@ -343,8 +343,8 @@ int dbcsr_amd_bcsr_dot(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd
 int dbcsr_amd_bcsr_norm2(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, int symmetric, double out[1], void* stream);
 
 /* Norms and vectors (src/ops/dbcsr_operations.F: dbcsr_norm / dbcsr_gershgorin_norm / dbcsr_maxabs_norm, dbcsr_get_diag, dbcsr_set_diag,
- * dbcsr_scale_by_vector): a result or an operand per FULL row or column of the matrix.  Same types, same answers as above (-10, -1; 0 for an empty matrix:
- * scalar outputs are then 0, the vector outputs of the sums and of _get_diag all zero).  out, diag and vec are DEVICE memory.  A vector over the rows has
+ * dbcsr_scale_by_vector; and the product of the matrix with a dense vector): a result or an operand per FULL row or column of the matrix.  Same types,
+ * same answers as above (-10, -1; 0 for an empty matrix: scalar outputs are then 0, the vector outputs of the sums and of _get_diag all zero).  out, diag and vec are DEVICE memory.  A vector over the rows has
  * sum(row_blk_size) elements, one over the columns sum(col_blk_size), in the order of the dense matrix; the element offsets of the block rows / columns are
  * formed on the device.  Sums are carried in double, one partial vector per wave of a block row / column, the partial vectors added in a fixed order: no
  * floating-point atomics, the same bits on every call.  All go by the index, use buffers of their own and leave a saved plan alone.
@@ -374,6 +374,20 @@ int dbcsr_amd_bcsr_gershgorin(void* handle, libsmm_acc_data_t datatype, const db
 int dbcsr_amd_bcsr_get_diag(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, void* diag, int64_t n, void* stream);
 int dbcsr_amd_bcsr_set_diag(void* handle, libsmm_acc_data_t datatype, dbcsr_amd_bcsr* m, const void* diag, int64_t n, void* stream);
 int dbcsr_amd_bcsr_scale_by_vector(void* handle, libsmm_acc_data_t datatype, dbcsr_amd_bcsr* m, const void* vec, int64_t n, int side, void* stream);
+/*   _matvec     y <- alpha op(A) x + beta y with dense DEVICE vectors x and y of the matrix' data type; trans 'N', 'T' or 'C' (conjugate transpose; real
+ *               data: 'T'), any other: -1.  x has one element per full column of op(A), y one per full row, in the order of the dense matrix.  kind -1: the
+ *               stored blocks only.  kind 0 ... 3 (S A H K; any other kind: -1): a stored triangle with a square block structure (nblkrows == nblkcols,
+ *               else -1), the product is that of the desymmetrized matrix -- a stored block (r, c), r != c, gives a x[c] to the rows of r and its twin
+ *               (a^T, -a^T, conj(a)^T, -conj(a)^T) x[r] to the rows of c; diagonal blocks are stored in full and count once; H and K on real data are S
+ *               and A.  Composed on the device of a pass by block row and a pass by block column (the latter for 'T' / 'C' and for the twins), as
+ *               _gershgorin is.  beta == 0: y is not read (a NaN in it does not reach the result).  alpha == 0: A and x are not read, y <- beta y in the
+ *               data's own precision; so for an empty matrix (0).  Every element of y below the full length is written, a full row that no stored
+ *               block touches gets beta y[i]; elements of a longer y behind the full length are left alone.  x and y must not overlap: -1 when
+ *               [x, x + n_x) and [y, y + n_y) intersect.  Products and sums in double / complex double (fp32 products are exact), alpha and beta applied in
+ *               double, one rounding to the data's type.  Every read of x stays below n_x, every write of y below n_y: a term whose entry of x would lie
+ *               behind n_x is not formed, an element of y at or behind n_y is not produced.  Asynchronous, no synchronisation. */
+int dbcsr_amd_bcsr_matvec(void* handle, libsmm_acc_data_t datatype, char trans, const double alpha[2], const dbcsr_amd_bcsr* a,
+  int kind /* -1: no symmetry; 0 ... 3: S A H K */, const void* x, int64_t n_x, const double beta[2], void* y, int64_t n_y, void* stream);
 
 /* Measurement helper (bench.py, roofline.fabric): what the L2 <-> Infinity-Cache fabric of the current device delivers, in TB/s -- a
  * plain streaming read of a 160 MB window by all CUs, and the block gather of the block-product dataflow (4232-byte blocks from

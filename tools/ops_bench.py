@@ -22,6 +22,15 @@ alternating:
   scale.R/.L  dbcsr_amd_bcsr_scale_by_vector of A on the right / left with a vector of ones (A is read and written)
   torch.mul   torch.mul(a.data, s, out=a.data) with a scalar: the same bytes through a kernel that is not ours, the yardstick of scale.R / scale.L
 
+  matvec.N/.T dbcsr_amd_bcsr_matvec of A with a vector of ones, y <- A x and y <- A^T x (element offsets, algebra_matvec_rows or the per-column lists and
+              algebra_matvec_cols, algebra_matvec_combine; asynchronous).  Yardstick: norm
+  matvec.S    the same of the stored triangle T as a symmetric matrix (row pass plus column pass off the diagonal: T's data is read twice).  Yardstick: norm.T
+
+With --matvec only norm, norm.T, the three matvec rows and the sums they are made from (gersh.N: the row pass without the reads of x; colnorm: the column
+pass without them; gersh.S: both) are timed, alternating, and the report has the ratios of the matvec rows alone:
+
+    python tools/ops_bench.py --matvec --alternations 7 --warmup 2 --out profiles/matrix_vector.txt
+
 With --colsums (lab build: DBCSR_AMD_LAB=1) only this is timed, alternating: norm, and dbcsr_amd_bcsr_col_sums of |x|^2 of A through an engine per form of
 algebra_col_sums (DBCSR_AMD_ALG_COLSUMS; csrc/mm_algebra.h): col.0 what ships, col.1 staging without the per-lane add loop, col.2 loads added in registers
 without LDS, col.3 no block walked (list build, launch, sum of the partial vectors), col.4 the lane-per-column form without staging; col.lists is col.3.
@@ -115,6 +124,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--colsums", action="store_true", help="the forms of algebra_col_sums against each other (lab build)")
+    ap.add_argument("--matvec", action="store_true", help="only the matrix-vector product, its yardsticks and the sums its passes are made from")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "ops_bench.py measures on the GPU"
@@ -128,6 +138,7 @@ def main():
     rng = np.random.default_rng(2)
     if args.colsums:
         return colsums(args, say, lines, rng, b, nb, st)
+    only = ("norm", "norm.T", "matvec.N", "matvec.T", "matvec.S", "gersh.N", "colnorm", "gersh.S") if args.matvec else None
     # the same-pattern pair
     mask = rng.random((nb, nb)) < args.fill_flat
     A, B = matrix_of(mask, b, 1), matrix_of(mask, b, 2)
@@ -144,7 +155,7 @@ def main():
     D = DbcsrMatrix(GA.row_blk_size, GA.col_blk_size, row_p, torch.empty(nblk.value, dtype=torch.int32, device="cuda"),
                     torch.empty(nblk.value, dtype=torch.int64, device="cuda"), torch.empty(nze.value, dtype=torch.float64, device="cuda"))
     gd = D.desc(out=True)
-    one, two = (C.c_double * 2)(1.0, 0.0), (C.c_double * 2)(beta, 0.0)
+    one, two, zero = (C.c_double * 2)(1.0, 0.0), (C.c_double * 2)(beta, 0.0), (C.c_double * 2)(0.0, 0.0)
     shared = int(np.count_nonzero(u < q))
     out2 = (C.c_double * 2)()
     a = A.desc()
@@ -185,10 +196,15 @@ def main():
         "scale.R": lambda: check(E.L.dbcsr_amd_bcsr_scale_by_vector(E.h, f64, C.byref(a), ones.data_ptr(), ones.numel(), 1, st.ptr)),
         "scale.L": lambda: check(E.L.dbcsr_amd_bcsr_scale_by_vector(E.h, f64, C.byref(a), ones.data_ptr(), ones.numel(), 0, st.ptr)),
         "torch.mul": lambda: torch.mul(A.data, 1.0, out=A.data),
+        "matvec.N": lambda: check(E.L.dbcsr_amd_bcsr_matvec(E.h, f64, b"N", one, C.byref(a), -1, ones.data_ptr(), ones.numel(), zero, colv.data_ptr(), colv.numel(), st.ptr)),
+        "matvec.T": lambda: check(E.L.dbcsr_amd_bcsr_matvec(E.h, f64, b"T", one, C.byref(a), -1, ones.data_ptr(), ones.numel(), zero, colv.data_ptr(), colv.numel(), st.ptr)),
+        "matvec.S": lambda: check(E.L.dbcsr_amd_bcsr_matvec(E.h, f64, b"N", one, C.byref(t_), 0, ones.data_ptr(), ones.numel(), zero, colv.data_ptr(), colv.numel(), st.ptr)),
     }
+    if only:
+        run = {k: run[k] for k in only}
     nbytes = {"flat": 24 * A.nze, "torch.add": 24 * A.nze, "flat.count": 0, "general": 8 * (GA.nze + GB.nze + nze.value), "count": 0, "norm": 8 * A.nze, "torch.norm": 8 * A.nze,
               "gersh.N": 8 * A.nze, "norm.T": 8 * T.nze, "gersh.S": 16 * T.nze, "colnorm": 8 * A.nze, "maxabs": 8 * A.nze, "scale.R": 16 * A.nze, "scale.L": 16 * A.nze,
-              "torch.mul": 16 * A.nze}
+              "torch.mul": 16 * A.nze, "matvec.N": 8 * A.nze, "matvec.T": 8 * A.nze, "matvec.S": 16 * T.nze}
     times = {k: [] for k in run}
     for step in range(args.warmup + args.alternations):
         for k in run:
@@ -205,6 +221,18 @@ def main():
         rate = ("%8.1f GB/s" % (1e-6 * nbytes[k] / med[k])) if nbytes[k] else "   (no data moved)"
         say("  %-10s  median %8.4f ms  min %8.4f  max %8.4f  spread %5.1f %%  %s   samples: %s"
             % (k, med[k], v[0], v[-1], 100 * (v[-1] - v[0]) / med[k], rate, " ".join("%.4f" % x for x in times[k])))
+    matvec_rows = (("matvec.N", "norm"), ("matvec.T", "norm"), ("matvec.S", "norm.T"))
+    if only:
+        say("")
+        say("matrix-vector product: time against the yardstick of the same run (median / median; spread of the ratio over the alternations, sample by sample);")
+        say("below them the sums whose walks the passes are, without the reads of x")
+        for k, y in matvec_rows + (("gersh.N", "norm"), ("colnorm", "norm"), ("gersh.S", "norm.T")):
+            r = sorted(x / z for x, z in zip(times[k], times[y]))
+            say("  %-8s / %-9s  %.2f   (per alternation %.2f ... %.2f)" % (k, y, med[k] / med[y], r[0], r[-1]))
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     flat_ms = med["flat"] - med["flat.count"]
     say("  flat kernel = flat - flat.count: %.4f ms, %.1f GB/s, %.2f of torch.add's rate" % (flat_ms, 1e-6 * nbytes["flat"] / flat_ms, med["torch.add"] / flat_ms))
     apply_ms = med["general"] - med["count"]
@@ -214,7 +242,7 @@ def main():
         % (flat_rate / torch_rate, nbytes["general"] / med["general"] / torch_rate, nbytes["general"] / apply_ms / torch_rate, med["torch.norm"] / med["norm"]))
     say("")
     say("norms and vectors: time against the yardstick of the same run (median / median; spread of the ratio over the alternations, sample by sample)")
-    for k, y in (("gersh.N", "norm"), ("colnorm", "norm"), ("maxabs", "norm"), ("gersh.S", "norm.T"), ("scale.R", "torch.mul"), ("scale.L", "torch.mul")):
+    for k, y in (("gersh.N", "norm"), ("colnorm", "norm"), ("maxabs", "norm"), ("gersh.S", "norm.T"), ("scale.R", "torch.mul"), ("scale.L", "torch.mul")) + matvec_rows:
         r = sorted(x / z for x, z in zip(times[k], times[y]))
         say("  %-8s / %-9s  %.2f   (per alternation %.2f ... %.2f)" % (k, y, med[k] / med[y], r[0], r[-1]))
     if args.out:
