@@ -1,7 +1,7 @@
 // mm_engine_algebra.h -- part of mm_engine.hip (included inside extern "C", after mm_engine_ops.h): the C-ABI operations between multiplies --
 // dbcsr_amd_bcsr_add_count / _add_apply, the pieces of dbcsr_add_on_diag (dbcsr_amd_bcsr_diag_count / _diag_fill / _diag_shift), dbcsr_amd_bcsr_trace,
-// _dot, _norm2, and the norms and vectors: dbcsr_amd_bcsr_maxabs, _row_sums, _col_sums, _gershgorin, _get_diag, _set_diag, _scale_by_vector, _matvec.
-// Kernels: mm_algebra.h.  The reductions, the diagonal pieces, the same-pattern add and the norms and vectors use buffers of their own (Engine::alg_*) and the
+// _dot, _norm2, and the norms and vectors: dbcsr_amd_bcsr_maxabs, _row_sums, _col_sums, _gershgorin, _get_diag, _set_diag, _scale_by_vector, _matvec, _multivec.
+// Kernels: mm_algebra.h, mm_multivec.h.  The reductions, the diagonal pieces, the same-pattern add and the norms and vectors use buffers of their own (Engine::alg_*) and the
 // scan's scratch, which no saved plan depends on (the checksum uses it the same way): they do NOT invalidate the plan.  The union add borrows the
 // symbolic phase's bitmaps and prefix arrays and invalidates it, as filter and crop do.
 #ifndef DBCSR_AMD_MM_ENGINE_ALGEBRA_H
@@ -612,6 +612,75 @@ int dbcsr_amd_bcsr_matvec(void* handle, libsmm_acc_data_t datatype, char trans, 
   const int64_t* total = trans == 'N' ? roff + a->nblkrows : coff + a->nblkcols;   // the full rows of op(A)
   DBCSR_AMD_BY_TYPE(matvec_launch, E, st, a, rp, cp, S_r, S_c, roff, coff, total, alpha, beta, mode, x, n_x, y, n_y);
   return check(hipGetLastError(), "dbcsr_amd_bcsr_matvec", __FILE__, __LINE__);
+}
+
+// ---- matrix times several dense vectors (kernels: mm_multivec.h) ---------------------------------------------------------------------------------------
+extern "C++" {
+// Waves per block row / column of the multivec passes.  A unit of (block row, sub) already brings one wave per tile of 16 right-hand sides, so row_split's
+// S is divided by the tile count: the number of waves stays near row_split's target, and with it the volume of the partial matrices (S n_y nrhs sums:
+// config 2's product, fp64, 47 partials at nrhs 16, 12 at nrhs 64 -- about 200 MB either way, 2.3 % of A's bytes, where 47 at nrhs 64 would be 9 %).
+static inline int multivec_split(int64_t nb, int64_t nblks, int ntiles) {
+  return std::max(1, (row_split(nb, nblks) + ntiles - 1) / ntiles);
+}
+
+// (the caller made alg_sums hold (S_r + S_c) n_y nrhs sums, the column list when the column pass is on, and the offsets)
+template <typename T>
+static void multivec_launch(Engine* E, hipStream_t st, const dbcsr_amd_bcsr* a, const MatvecPass& rp, const MatvecPass& cp, int S_r, int S_c,
+                            const int64_t* roff, const int64_t* coff, const int64_t* total, const double alpha[2], const double beta[2], int mode,
+                            int nrhs, const void* x, int64_t n_x, int64_t ldx, void* y, int64_t n_y, int64_t ldy) {
+  using Acc = typename MatvecAcc<T>::type;
+  Acc* sums = reinterpret_cast<Acc*>(E->alg_sums.p);
+  const int nbr = a->nblkrows, nbc = a->nblkcols, vec_ok = aligned16(a->data);
+  int wmax = kMultivecWaves;
+#ifdef DBCSR_AMD_EXPERIMENTS
+  if (E->ls.multivec_waves >= 1 && E->ls.multivec_waves <= kMultivecWaves) wmax = E->ls.multivec_waves;   // DBCSR_AMD_MULTIVEC_WAVES (1: independent waves)
+#endif
+  const int ntiles = (nrhs + kMultivecTile - 1) / kMultivecTile, W = std::min(ntiles, wmax), G = (ntiles + W - 1) / W;
+  const size_t lds = (size_t)W * (kMultivecABytes + kMultivecXBytes);
+  if (S_r > 0)
+    hipLaunchKernelGGL((algebra_multivec_rows<T>), dim3((unsigned)((int64_t)nbr * S_r * G)), dim3(64 * W), lds, st, a->row_p, a->col_i, a->blk_p,
+                       static_cast<const T*>(a->data), a->row_blk_size, a->col_blk_size, roff, coff, nbr, S_r, G, rp.conj, rp.skip_diag, vec_ok,
+                       static_cast<const T*>(x), n_x, ldx, nrhs, n_y, sums);
+  if (S_c > 0)
+    hipLaunchKernelGGL((algebra_multivec_cols<T>), dim3((unsigned)((int64_t)nbc * S_c * G)), dim3(64 * W), lds, st, E->alg_col_p.p, E->alg_list.p, a->blk_p,
+                       static_cast<const T*>(a->data), a->row_blk_size, a->col_blk_size, coff, roff, nbc, S_c, G, cp.conj, cp.skip_diag, vec_ok,
+                       static_cast<const T*>(x), n_x, ldx, nrhs, n_y, sums + (size_t)S_r * (size_t)n_y * nrhs);
+  hipLaunchKernelGGL((algebra_multivec_combine<T>), grid_for(n_y * nrhs), dim3(256), 0, st, sums, S_r, S_c, rp.sign, cp.sign, n_y, nrhs, ldy, total,
+                     algebra_scalar<Acc>(alpha), algebra_scalar<Acc>(beta), mode, static_cast<T*>(y));
+}
+}  // extern "C++"
+
+int dbcsr_amd_bcsr_multivec(void* handle, libsmm_acc_data_t datatype, char trans, const double alpha[2], const dbcsr_amd_bcsr* a, int kind, int nrhs,
+                            const void* x, int64_t n_x, int64_t ldx, const double beta[2], void* y, int64_t n_y, int64_t ldy, void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E || !alpha || !a || !beta || n_x < 0 || n_y < 0 || nrhs < 0 || ldx < nrhs || ldy < nrhs) return -1;
+  if (nrhs > 0 && ((n_x > 0 && !x) || (n_y > 0 && !y))) return -1;
+  if (trans != 'N' && trans != 'T' && trans != 'C') return -1;
+  if (kind < -1 || kind > 3 || (kind >= 0 && a->nblkrows != a->nblkcols)) return -1;
+  if (!algebra_type(datatype)) return -10;
+  const size_t esize = datatype == dbcsr_type_real_8 ? 8 : datatype == dbcsr_type_real_4 ? 4 : 16;
+  if (nrhs > 0 && n_x > 0 && n_y > 0) {   // the element ranges of X and Y must not overlap
+    const uintptr_t x0 = reinterpret_cast<uintptr_t>(x), y0 = reinterpret_cast<uintptr_t>(y);
+    const uintptr_t x1 = x0 + esize * ((size_t)(n_x - 1) * (size_t)ldx + (size_t)nrhs), y1 = y0 + esize * ((size_t)(n_y - 1) * (size_t)ldy + (size_t)nrhs);
+    if (x0 < y1 && y0 < x1) return -1;
+  }
+  hipStream_t st = stream_of(stream);
+  if (nrhs == 0 || n_y == 0 || a->nblkrows == 0 || a->nblkcols == 0) return 0;   // (no element of Y below the full length: nothing to write)
+  const bool zc = datatype == dbcsr_type_complex_8;
+  const bool alpha_zero = alpha[0] == 0.0 && (!zc || alpha[1] == 0.0), beta_zero = beta[0] == 0.0 && (!zc || beta[1] == 0.0);
+  const bool product = !alpha_zero && a->nblks > 0;   // alpha == 0: A and X are not read; an empty matrix: Y <- beta Y
+  const int mode = (product ? 0 : kMatvecNoProduct) | (beta_zero ? kMatvecBetaZero : 0);
+  MatvecPass rp = {0, 0, 0, 1.0}, cp = rp;
+  if (product) matvec_passes(kind, trans, &rp, &cp);
+  const int ntiles = (nrhs + kMultivecTile - 1) / kMultivecTile, G = ntiles;   // (workgroups per block row and sub: at most one per tile)
+  const int S_r = rp.on ? multivec_split(a->nblkrows, a->nblks, ntiles) : 0, S_c = cp.on ? multivec_split(a->nblkcols, a->nblks, ntiles) : 0;
+  if ((int64_t)std::max(a->nblkrows, a->nblkcols) * std::max(S_r, S_c) * G > INT32_MAX || n_y > (int64_t)INT32_MAX * 256 / nrhs) return -1;   // (the grids)
+  const int64_t *roff = nullptr, *coff = nullptr;
+  if (E->alg_sums.ensure((size_t)(S_r + S_c) * (size_t)n_y * (size_t)nrhs * (zc ? 2 : 1) + 2) || vector_offsets(E, st, a, &roff, &coff)) return -1;
+  if (cp.on && col_list_build(E, st, a)) return -1;
+  const int64_t* total = trans == 'N' ? roff + a->nblkrows : coff + a->nblkcols;   // the full rows of op(A)
+  DBCSR_AMD_BY_TYPE(multivec_launch, E, st, a, rp, cp, S_r, S_c, roff, coff, total, alpha, beta, mode, nrhs, x, n_x, ldx, y, n_y, ldy);
+  return check(hipGetLastError(), "dbcsr_amd_bcsr_multivec", __FILE__, __LINE__);
 }
 #undef DBCSR_AMD_BY_TYPE
 

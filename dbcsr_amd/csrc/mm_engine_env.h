@@ -48,6 +48,7 @@ static void engine_read_env(Engine* E) {
   }
   if (const char* k = getenv("DBCSR_AMD_MM_DBG")) E->lab.dbg = atoi(k);
   if (const char* k = getenv("DBCSR_AMD_ALG_COLSUMS")) E->ls.alg_col_variant = atoi(k);
+  if (const char* k = getenv("DBCSR_AMD_MULTIVEC_WAVES")) E->ls.multivec_waves = atoi(k);
   {
     const char* k = getenv("DBCSR_AMD_MM_POISON");  // (process-wide: the engines created from now on)
     g_devbuf_poison = k ? (atoi(k) & 255) : -1;

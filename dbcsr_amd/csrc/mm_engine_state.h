@@ -65,6 +65,9 @@ struct LabState {
 
   // norms and vectors: DBCSR_AMD_ALG_COLSUMS = 1 ... 4, the ablations of algebra_col_sums and its lane-per-column form (mm_algebra.h)
   int alg_col_variant = 0;
+  // matrix times several vectors: DBCSR_AMD_MULTIVEC_WAVES = 1 ... 4, the waves (tiles of 16 right-hand sides) of a workgroup that share a staged
+  // block; 1: independent waves, every tile loads the block itself (mm_multivec.h; profiles/matrix_multivec.txt)
+  int multivec_waves = 0;
 
   void forget_plan() { tile_built = band_built = group_built = false; }
 };

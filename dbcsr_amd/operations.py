@@ -13,6 +13,7 @@
     dbcsr_get_diag(matrix) / dbcsr_set_diag(matrix, diag)       the diagonal as a device vector
     dbcsr_scale_by_vector(matrix, alpha, side)                  A <- A*diag(alpha) ("right") or diag(alpha)*A ("left")
     dbcsr_matvec(matrix, vec_in, vec_out, alpha, beta, trans)   y <- alpha*op(A)*x + beta*y with dense device vectors (not a mirror, see there)
+    dbcsr_multivec(matrix, vecs_in, vecs_out, alpha, beta, trans)  Y <- alpha*op(A)*X + beta*Y with nrhs dense device vectors at once: A is read once
 
 Same argument names and error behaviour; the work is done by the C-ABI engine (include/dbcsr_amd_mm.h, "Matrix algebra between
 multiplies") on the GPU, for float64, float32 and complex128 data.  One rank / one device here: of a distributed matrix trace, dot
@@ -395,3 +396,66 @@ def dbcsr_matvec(matrix, vec_in, vec_out=None, alpha=1.0, beta=0.0, trans="N", e
     if rc != 0:
         raise RuntimeError("dbcsr_amd_bcsr_matvec failed (%d)" % rc)
     return vec_out
+
+
+def _check_vectors(name, matrix, vecs, n):
+    """a device matrix of n rows, one right-hand side per column, of the matrix' data type, its rows contiguous: checked before any call of the library"""
+    if not isinstance(vecs, torch.Tensor):
+        raise TypeError("%s: the vectors must be a torch tensor" % name)
+    if vecs.dtype != matrix.dtype:
+        raise TypeError("%s: the vectors have data type %r, expected %r" % (name, vecs.dtype, matrix.dtype))
+    if vecs.device != matrix.row_p.device:
+        raise ValueError("%s: the vectors are not on the matrix' device" % name)
+    if vecs.dim() != 2 or vecs.shape[0] != n:
+        raise ValueError("%s: the vectors must be a 2-D tensor with %d rows, one right-hand side per column" % (name, n))
+    nrhs = vecs.shape[1]
+    if nrhs > 1 and vecs.stride(1) != 1:
+        raise ValueError("%s: the vectors must have stride(1) == 1 (the right-hand sides of one row are consecutive)" % name)
+    if n > 1 and vecs.stride(0) < nrhs:
+        raise ValueError("%s: the vectors must have stride(0) >= nrhs" % name)
+    return nrhs, (vecs.stride(0) if n > 1 else nrhs)
+
+
+def dbcsr_multivec(matrix, vecs_in, vecs_out=None, alpha=1.0, beta=0.0, trans="N", engine=None, stream=None):
+    """vecs_out <- alpha * op(A) * vecs_in + beta * vecs_out with nrhs right-hand sides at once: dbcsr_matvec for the columns of a dense device matrix,
+    with A read once for all of them -- what block Lanczos / LOBPCG, a Chebyshev filter on a block of vectors, subspace iteration or the product of a
+    sparse matrix with a tall-and-skinny coefficient matrix need.  vecs_in is (n_x, nrhs), vecs_out (n_y, nrhs): 2-D device tensors of the matrix'
+    data type with stride(1) == 1 and stride(0) >= nrhs -- a contiguous tensor, or a column slice of a wider one.  trans, the symmetries, alpha == 0
+    and beta == 0 are dbcsr_matvec's, per column; so are the checks.  The padding columns of a slice are never written.  vecs_out=None (then beta
+    must be 0) allocates (n_y, nrhs) on the matrix' device and stream.  One column is served by the same kernels, not by dbcsr_matvec.  The two
+    tensors must not overlap.  Asynchronous on the stream; returns vecs_out."""
+    sym = _check_symmetry("dbcsr_multivec", matrix)
+    if trans not in ("N", "T", "C"):
+        raise ValueError("dbcsr_multivec: trans must be 'N', 'T' or 'C', got %r" % (trans,))
+    matrix.dtype_code
+    kind = -1
+    if sym != "N":
+        kind = matrix.symmetry_kind()
+        _check_square("dbcsr_multivec", matrix)
+    _check_scalar("dbcsr_multivec", matrix, alpha, beta)
+    n_rows, n_cols = _full_size(matrix.row_blk_size), _full_size(matrix.col_blk_size)
+    n_x, n_y = (n_cols, n_rows) if trans == "N" else (n_rows, n_cols)
+    nrhs, ldx = _check_vectors("dbcsr_multivec", matrix, vecs_in, n_x)
+    if vecs_out is None:
+        if beta != 0:
+            raise ValueError("dbcsr_multivec: beta != 0 needs a vecs_out")
+        ldy = nrhs
+    else:
+        nout, ldy = _check_vectors("dbcsr_multivec", matrix, vecs_out, n_y)
+        if nout != nrhs:
+            raise ValueError("dbcsr_multivec: vecs_in has %d right-hand sides, vecs_out %d" % (nrhs, nout))
+        size = vecs_in.element_size()
+        x0, y0 = vecs_in.data_ptr(), vecs_out.data_ptr()
+        if nrhs and n_x and n_y and x0 < y0 + size * ((n_y - 1) * ldy + nrhs) and y0 < x0 + size * ((n_x - 1) * ldx + nrhs):
+            raise ValueError("dbcsr_multivec: vecs_in and vecs_out overlap")
+    E = engine or default_engine()
+    st = StreamHandle(stream)
+    if vecs_out is None:
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            vecs_out = torch.empty((n_y, nrhs), dtype=matrix.dtype, device=matrix.row_p.device)
+    d = matrix.desc()
+    rc = E.L.dbcsr_amd_bcsr_multivec(E.h, matrix.dtype_code, trans.encode(), _z(alpha), C.byref(d), kind, nrhs, vecs_in.data_ptr() if n_x and nrhs else None,
+                                     n_x, ldx, _z(beta), vecs_out.data_ptr() if n_y and nrhs else None, n_y, ldy, st.ptr)
+    if rc != 0:
+        raise RuntimeError("dbcsr_amd_bcsr_multivec failed (%d)" % rc)
+    return vecs_out

@@ -388,6 +388,21 @@ int dbcsr_amd_bcsr_scale_by_vector(void* handle, libsmm_acc_data_t datatype, dbc
  *               behind n_x is not formed, an element of y at or behind n_y is not produced.  Asynchronous, no synchronisation. */
 int dbcsr_amd_bcsr_matvec(void* handle, libsmm_acc_data_t datatype, char trans, const double alpha[2], const dbcsr_amd_bcsr* a,
   int kind /* -1: no symmetry; 0 ... 3: S A H K */, const void* x, int64_t n_x, const double beta[2], void* y, int64_t n_y, void* stream);
+/*   _multivec   Y <- alpha op(A) X + beta Y with nrhs right-hand sides handled together: A is read once for all of them.  X is n_x x nrhs, Y is
+ *               n_y x nrhs, dense DEVICE matrices of the matrix' data type stored ROW BY ROW: element (i, v) at i ld + v, ld >= nrhs (a contiguous
+ *               (n, nrhs) array has ld = nrhs, a column slice of a wider basis a larger ld) -- the layout in which the nrhs entries one element of A
+ *               meets are consecutive.  trans, kind and every rule of _matvec hold per column: products and sums in double / complex double, one
+ *               rounding to the data's type; beta == 0: Y is not read; alpha == 0 or an empty matrix: A and X are not read, Y <- beta Y in the data's
+ *               own precision; a full row that no stored block touches gets beta y; no floating-point atomics, the same bits on every call;
+ *               asynchronous, no synchronisation; buffers of its own, a saved plan stays.  -1 for a null argument, a bad trans or kind, kind >= 0 with
+ *               nblkrows != nblkcols, nrhs < 0, ldx < nrhs or ldy < nrhs, and when the element ranges [x, x + (n_x - 1) ldx + nrhs) and
+ *               [y, y + (n_y - 1) ldy + nrhs) intersect; -10 for a data type the algebra does not know; 0 with nothing written for nrhs == 0 or
+ *               n_y == 0.  Every read of X stays in rows below n_x and columns below nrhs (a term whose row of X would lie behind n_x is not formed),
+ *               every write of Y in rows below n_y and below the full row count of op(A) and in columns below nrhs: the padding columns
+ *               nrhs ... ld - 1 of Y are never written.  One column (nrhs == 1) is served by the same kernels, not by _matvec. */
+int dbcsr_amd_bcsr_multivec(void* handle, libsmm_acc_data_t datatype, char trans, const double alpha[2], const dbcsr_amd_bcsr* a,
+  int kind /* -1; 0 ... 3: S A H K */, int nrhs, const void* x, int64_t n_x, int64_t ldx, const double beta[2], void* y, int64_t n_y, int64_t ldy,
+  void* stream);
 
 /* Measurement helper (bench.py, roofline.fabric): what the L2 <-> Infinity-Cache fabric of the current device delivers, in TB/s -- a
  * plain streaming read of a 160 MB window by all CUs, and the block gather of the block-product dataflow (4232-byte blocks from

@@ -35,6 +35,17 @@ With --colsums (lab build: DBCSR_AMD_LAB=1) only this is timed, alternating: nor
 algebra_col_sums (DBCSR_AMD_ALG_COLSUMS; csrc/mm_algebra.h): col.0 what ships, col.1 staging without the per-lane add loop, col.2 loads added in registers
 without LDS, col.3 no block walked (list build, launch, sum of the partial vectors), col.4 the lane-per-column form without staging; col.lists is col.3.
 
+With --multivec only the matrix times several dense vectors is timed (dbcsr_amd_bcsr_multivec, kernels of dbcsr_amd/csrc/mm_multivec.h), alternating with
+its yardsticks: norm (one read of A), matvec.N / matvec.T (the existing code, one right-hand side per call), multivec.N at nrhs 1, 4, 8, 16, 32, 64,
+multivec.T at 8 and 16, multivec.S at 16 (the stored triangle T as a symmetric matrix) against norm.T.  X is a contiguous (n, nrhs) tensor of ones.  The
+report has multivec(k) / norm, the time per column multivec(k) / k, the condition multivec(k) < k * matvec for k >= 4 in every alternation, and the split
+S with the volume of the partial matrices:
+
+    python tools/ops_bench.py --multivec --alternations 7 --warmup 2 --out profiles/matrix_multivec.txt
+
+With DBCSR_AMD_LAB=1 it also times multivec.N at 32 and 64 through an engine with DBCSR_AMD_MULTIVEC_WAVES=1 (rows ind.N: independent waves, every
+tile of 16 right-hand sides loads the block itself, against the shared staging of what ships).
+
 A sample is `--reps` calls back to back between two device events, divided by reps.  Bytes are counted from the shapes: 8 * (elements read + elements
 written) of the data areas, index arrays left out.  Spread = (max - min) / median over the samples."""
 import argparse
@@ -114,6 +125,101 @@ def colsums(args, say, lines, rng, b, nb, st):
             f.write("\n".join(lines) + "\n")
 
 
+def multivec(args, say, lines, rng, b, nb, st):
+    lab = L.want_lab()
+    E = MultiplyEngine(lab=True) if lab else MultiplyEngine()
+    mask = rng.random((nb, nb)) < args.fill_flat
+    A, T = matrix_of(mask, b, 1), matrix_of(np.triu(mask), b, 5)
+    a, t_ = A.desc(), T.desc()
+    f64 = L.dbcsr_type_real_8
+    n = nb * b
+    one, zero = (C.c_double * 2)(1.0, 0.0), (C.c_double * 2)(0.0, 0.0)
+    out2 = (C.c_double * 2)()
+    ones = torch.ones(n, dtype=torch.float64, device="cuda")
+    colv = torch.empty(n, dtype=torch.float64, device="cuda")
+    kmax = 64
+    X = torch.ones(n * kmax, dtype=torch.float64, device="cuda")
+    Y = torch.empty(n * kmax, dtype=torch.float64, device="cuda")
+    check = lambda rc: rc == 0 or sys.exit("a library call failed (%d)" % rc)
+
+    def mv(e, trans, d, kind, k):
+        return lambda: check(e.L.dbcsr_amd_bcsr_multivec(e.h, f64, trans, one, C.byref(d), kind, k, X.data_ptr(), n, k, zero, Y.data_ptr(), n, k, st.ptr))
+
+    run = {
+        "norm": lambda: check(E.L.dbcsr_amd_bcsr_norm2(E.h, f64, C.byref(a), 0, out2, st.ptr)),
+        "norm.T": lambda: check(E.L.dbcsr_amd_bcsr_norm2(E.h, f64, C.byref(t_), 1, out2, st.ptr)),
+        "matvec.N": lambda: check(E.L.dbcsr_amd_bcsr_matvec(E.h, f64, b"N", one, C.byref(a), -1, ones.data_ptr(), n, zero, colv.data_ptr(), n, st.ptr)),
+        "matvec.T": lambda: check(E.L.dbcsr_amd_bcsr_matvec(E.h, f64, b"T", one, C.byref(a), -1, ones.data_ptr(), n, zero, colv.data_ptr(), n, st.ptr)),
+    }
+    width = {}
+    for k in (1, 4, 8, 16, 32, 64):
+        run["multivec.N.%d" % k] = mv(E, b"N", a, -1, k)
+        width["multivec.N.%d" % k] = k
+    for k in (8, 16):
+        run["multivec.T.%d" % k] = mv(E, b"T", a, -1, k)
+        width["multivec.T.%d" % k] = k
+    run["multivec.S.16"] = mv(E, b"N", t_, 0, 16)
+    width["multivec.S.16"] = 16
+    if lab:
+        os.environ["DBCSR_AMD_MULTIVEC_WAVES"] = "1"
+        E1 = MultiplyEngine(lab=True)
+        del os.environ["DBCSR_AMD_MULTIVEC_WAVES"]
+        for k in (32, 64):
+            run["ind.N.%d" % k] = mv(E1, b"N", a, -1, k)
+            width["ind.N.%d" % k] = k
+    # the product of ones: every row of A x, in every column, is the row sum; the multivec and the matvec must agree on it to rounding
+    run["matvec.N"]()
+    run["multivec.N.64"]()
+    torch.cuda.synchronize()
+    worst = float((Y.view(n, kmax) - colv[:, None]).abs().max() / colv.abs().max())
+    say("multivec.N.64 against matvec.N on vectors of ones: largest difference %.2e of the largest row sum" % worst)
+    times = {k: [] for k in run}
+    for step in range(args.warmup + args.alternations):
+        for k in run:
+            t = sample(run[k], args.reps)
+            if step >= args.warmup:
+                times[k].append(t)
+    say("")
+    say("A: %d blocks, %.1f MB; T (stored triangle): %d blocks, %.1f MB" % (A.nblks, 8e-6 * A.nze, T.nblks, 8e-6 * T.nze))
+    med = {}
+    for k in run:
+        v = sorted(times[k])
+        med[k] = v[len(v) // 2]
+        nbytes = (16 if k.endswith(".S.16") else 8) * (T.nze if (k == "norm.T" or ".S." in k) else A.nze)
+        say("  %-14s  median %8.4f ms  min %8.4f  max %8.4f  spread %5.1f %%  %8.1f GB/s   samples: %s"
+            % (k, med[k], v[0], v[-1], 100 * (v[-1] - v[0]) / med[k], 1e-6 * nbytes / med[k], " ".join("%.4f" % x for x in times[k])))
+    say("")
+    say("time against one read of the matrix (median / median; the ratio per alternation, sample by sample), and per right-hand side")
+    for k in run:
+        if k not in width:
+            continue
+        y = "norm.T" if ".S." in k else "norm"
+        r = sorted(x / z for x, z in zip(times[k], times[y]))
+        say("  %-14s / %-6s  %5.2f   (per alternation %.2f ... %.2f)   %8.4f ms per column" % (k, y, med[k] / med[y], r[0], r[-1], med[k] / width[k]))
+    say("")
+    say("condition: multivec(k) below k * matvec in every alternation, k >= 4")
+    ok = True
+    for k in run:
+        if k not in width or width[k] < 4 or ".S." in k or k.startswith("ind."):
+            continue
+        y = "matvec.T" if ".T." in k else "matvec.N"
+        r = sorted(x / (width[k] * z) for x, z in zip(times[k], times[y]))
+        ok = ok and r[-1] < 1.0
+        say("  %-14s / (%2d * %s)  %.3f ... %.3f   %s" % (k, width[k], y, r[0], r[-1], "holds" if r[-1] < 1.0 else "FAILS"))
+    say("  the condition %s" % ("holds" if ok else "FAILS"))
+    say("")
+    say("split S (waves per block row / column and tile; as dbcsr_amd/csrc/mm_engine_algebra.h: multivec_split) and the volume of the partial matrices")
+    row_split = max(1, min(-(-65536 // nb), A.nblks // nb, 64))
+    for k in (1, 4, 8, 16, 32, 64):
+        tiles = -(-k // 16)
+        S = max(1, -(-row_split // tiles))
+        vol = 8.0 * S * n * k
+        say("  nrhs %2d: %d tile(s), S = %2d, %7.1f MB written and read once = %.2f %% of A" % (k, tiles, S, 1e-6 * vol, 100.0 * vol / (8.0 * A.nze)))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=32768)
@@ -125,6 +231,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--colsums", action="store_true", help="the forms of algebra_col_sums against each other (lab build)")
     ap.add_argument("--matvec", action="store_true", help="only the matrix-vector product, its yardsticks and the sums its passes are made from")
+    ap.add_argument("--multivec", action="store_true", help="only the matrix times several dense vectors and its yardsticks")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "ops_bench.py measures on the GPU"
@@ -138,6 +245,8 @@ def main():
     rng = np.random.default_rng(2)
     if args.colsums:
         return colsums(args, say, lines, rng, b, nb, st)
+    if args.multivec:
+        return multivec(args, say, lines, rng, b, nb, st)
     only = ("norm", "norm.T", "matvec.N", "matvec.T", "matvec.S", "gersh.N", "colnorm", "gersh.S") if args.matvec else None
     # the same-pattern pair
     mask = rng.random((nb, nb)) < args.fill_flat
