@@ -98,14 +98,24 @@ LAB_SWITCHES = ("DBCSR_AMD_MM_HOT_VARIANT", "DBCSR_AMD_MM_HOT_PERSISTENT", "DBCS
                 "DBCSR_AMD_MM_DBG", "DBCSR_AMD_MM_LDS_PAD", "DBCSR_AMD_MM_ROW_GROUP")
 
 
-def run_case(monkeypatch, env, case, dtype, tol, expect, alpha=0.7, beta=1.3, retain=False, in_place_twice=False):
-    for k in ("DBCSR_AMD_MM_KERNEL", "DBCSR_AMD_MM_HOT", "DBCSR_AMD_MM_TINY", "DBCSR_AMD_MM_PIPE_G", "DBCSR_AMD_MM_SYMBOLIC", "DBCSR_AMD_MM_CLASSES", "DBCSR_AMD_MM_CLASS_G", "DBCSR_AMD_MM_WORK", "DBCSR_AMD_MM_WG_WAVES", "DBCSR_AMD_MM_CLASS_STREAMS", "DBCSR_AMD_MM_HOT_VARIANT", "DBCSR_AMD_MM_HOT_PERSISTENT", "DBCSR_AMD_MM_HOT_XCDS", "DBCSR_AMD_MM_F32_DIRECT", "DBCSR_AMD_MM_BIG", "DBCSR_AMD_MM_MID"):
+SWITCHES = ("DBCSR_AMD_MM_KERNEL", "DBCSR_AMD_MM_HOT", "DBCSR_AMD_MM_TINY", "DBCSR_AMD_MM_PIPE_G", "DBCSR_AMD_MM_SYMBOLIC", "DBCSR_AMD_MM_CLASSES", "DBCSR_AMD_MM_CLASS_G",
+            "DBCSR_AMD_MM_WORK", "DBCSR_AMD_MM_WG_WAVES", "DBCSR_AMD_MM_CLASS_STREAMS", "DBCSR_AMD_MM_HOT_VARIANT", "DBCSR_AMD_MM_HOT_PERSISTENT", "DBCSR_AMD_MM_HOT_XCDS",
+            "DBCSR_AMD_MM_F32_DIRECT", "DBCSR_AMD_MM_BIG", "DBCSR_AMD_MM_MID")
+
+
+def engine_for(monkeypatch, env, clear=()):
+    """an engine made under exactly the switches of env (every other switch of SWITCHES and of clear is taken out of the environment first)"""
+    for k in SWITCHES + tuple(clear):
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     # the switches of the experimental variants exist in the lab build only (dbcsr_amd/csrc/Makefile); everything else runs on the shipping one
     lab = any(k in LAB_SWITCHES for k in env) or env.get("DBCSR_AMD_MM_KERNEL", "").startswith("dma")
-    eng = MultiplyEngine(lab=lab)  # reads the switches now
+    return MultiplyEngine(lab=lab)  # reads the switches now
+
+
+def run_case(monkeypatch, env, case, dtype, tol, expect, alpha=0.7, beta=1.3, retain=False, in_place_twice=False):
+    eng = engine_for(monkeypatch, env)
     A, B, Cm = O.perf_case(*case)
     ref, info = O.multiply("N", "N", alpha, A, B, beta, Cm, retain_sparsity=retain)
     cast = lambda M: O.Bcsr(M.row_sizes, M.col_sizes, M.row_p, M.col_i, M.blk_p, M.data.astype(dtype))
@@ -145,7 +155,7 @@ F32_23 = (23 * 20 + 16, 23 * 18 + 16, 23 * 22 + 16, 0.6, 0.6, 0.7, [1, 23], [1, 
 F32_MIXED = (300, 280, 260, 0.5, 0.5, 0.6, [1, 13, 1, 32, 1, 7], [1, 23, 1, 32], [1, 13, 1, 32, 1, 9])
 
 
-@pytest.mark.parametrize("env,case,expect", [
+F32_VARIANTS = [
     ({}, F32, "mm_numeric_f32_direct<32,32,32>"),
     ({}, F32_TAILS, "mm_numeric_f32_direct<32,32,32>"),   # tail blocks: C blocks of other sizes and products with another inner dimension
     ({}, F32_16, "mm_numeric_f32_direct<16,16,16>"),
@@ -164,6 +174,9 @@ F32_MIXED = (300, 280, 260, 0.5, 0.5, 0.6, [1, 13, 1, 32, 1, 7], [1, 23, 1, 32],
     ({"DBCSR_AMD_MM_WG_WAVES": "2"}, F32_16, "mm_numeric_f32_direct<16,16,16>"),
     ({"DBCSR_AMD_MM_WG_WAVES": "2"}, F32_MIXED, "mm_numeric_f32_lds"),
     ({"DBCSR_AMD_MM_WG_WAVES": "4", "DBCSR_AMD_MM_CLASSES": "2"}, F32_MIXED, "mm_numeric_f32_lds[per class"),
-], ids=lambda v: "-".join("%s=%s" % (k[13:], x) for k, x in v.items()) if isinstance(v, dict) else None)
+]
+
+
+@pytest.mark.parametrize("env,case,expect", F32_VARIANTS, ids=lambda v: "-".join("%s=%s" % (k[13:], x) for k, x in v.items()) if isinstance(v, dict) else None)
 def test_fp32_variant_matches_oracle(monkeypatch, env, case, expect):
     run_case(monkeypatch, env, case, np.float32, 2e-5, expect, alpha=1.0, beta=1.0)
