@@ -386,7 +386,8 @@ twin_fill_z64(const int* __restrict__ s_row_p, const int* __restrict__ s_col_i, 
 
 __global__ void store_scalar_f64(double* __restrict__ p, double v) { *p = v; }
 
-// ---- block filter (dbcsr_mm_multrec.F:694-748 multrec_filtering / dbcsr_filter): drop blocks with ||blk||^2 < eps^2
+// ---- block filter (dbcsr_mm_multrec.F:694-748 multrec_filtering / dbcsr_filter): drop blocks with ||blk||^2 < eps^2.  The rule is the DROP: a block
+// whose norm is NaN is not below the threshold and stays, as in the reference (a NaN in the product must not vanish with its block)
 __global__ void __launch_bounds__(256) filter_flags(const double* __restrict__ norms64, int64_t nblks, const int* __restrict__ row_p,
                                                     const int* __restrict__ col_i, const int* __restrict__ rs, const int* __restrict__ cs,
                                                     int nbr, double eps2, int* __restrict__ keep, int* __restrict__ blk_nze,
@@ -397,7 +398,7 @@ __global__ void __launch_bounds__(256) filter_flags(const double* __restrict__ n
   if (row >= nbr) return;
   int cnt = 0;
   for (int b = row_p[row] + lane; b < row_p[row + 1]; b += 64) {
-    const int k = norms64[b] >= eps2 ? 1 : 0;
+    const int k = !(norms64[b] < eps2) ? 1 : 0;
     keep[b] = k;
     blk_nze[b] = k ? rs[row] * cs[col_i[b]] : 0;
     cnt += k;

@@ -72,7 +72,8 @@ constexpr unsigned kBandLanded = 32u;
 // compile-time offset; single ds_read_b64 (volatile: never paired into ds_read2_b64, which costs 8 LDS cycles against 2 x 2).  No
 // clamping: a lane whose row (column) is past the block reads a neighbouring element or whatever follows the slot and only pollutes
 // accumulator rows (columns) that are never stored; in the last k step of a K that is not a multiple of 4 the lanes past the end get an
-// exact zero on the A side and a finite B value (element (0, col + 1), or the zero padding the masked last DMA piece leaves).
+// exact zero on BOTH sides (what they read of B -- element (0, col + 1), or the zero padding the masked last DMA piece leaves -- may be Inf or NaN,
+// and 0 x Inf is NaN).
 template <int M, int N, int K>
 __device__ __forceinline__ void band_frags(int s, const double* pa, const double* pb, bool ktail_dead, double (&av)[3], double (&bv)[3]) {
   constexpr int KS = (K + 3) / 4;
@@ -82,7 +83,10 @@ __device__ __forceinline__ void band_frags(int s, const double* pa, const double
     if (s == KS - 1 && (K & 3)) av[a] = ktail_dead ? 0.0 : av[a];
   }
 #pragma unroll
-  for (int c = 0; c < 3; ++c) bv[c] = *(const volatile double __attribute__((address_space(3)))*)(pb + 8 * K * c + 4 * s);
+  for (int c = 0; c < 3; ++c) {
+    bv[c] = *(const volatile double __attribute__((address_space(3)))*)(pb + 8 * K * c + 4 * s);
+    if (s == KS - 1 && (K & 3)) bv[c] = ktail_dead ? 0.0 : bv[c];
+  }
 }
 
 __device__ __forceinline__ void band_mfma9(double (&acc)[3][3], const double (&av)[3], const double (&bv)[3]) {

@@ -103,7 +103,10 @@ __device__ __forceinline__ void cblock_f64_dma(const Desc& d, const Entry* __res
         if (s == KS - 1 && (K & 3)) av[a] = ktail_dead ? 0.0 : av[a];
       }
 #pragma unroll
-      for (int c = 0; c < NC; ++c) bv[c] = (s == KS - 1 && (K & 3)) ? sl[obt[c]] : sl[ob[c] + 4 * s];
+      for (int c = 0; c < NC; ++c) {
+        bv[c] = (s == KS - 1 && (K & 3)) ? sl[obt[c]] : sl[ob[c] + 4 * s];
+        if (s == KS - 1 && (K & 3)) bv[c] = ktail_dead ? 0.0 : bv[c];   // both factors a true zero: element (0, col) may be Inf, and 0 x Inf is NaN
+      }
 #pragma unroll
       for (int a = 0; a < MA; ++a)
 #pragma unroll

@@ -208,18 +208,20 @@ __device__ __forceinline__ void cblock_f64_classes(const Desc& d, const Entry fi
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       pb[c] = reinterpret_cast<const double*>(lds_b) + L.kq + BP * colc[c];
-      const int kt = 4 * (KS - 1) + L.kq;  // last step when K is not a multiple of 4: lanes past the end read (0, col); A's padding is zero
+      const int kt = 4 * (KS - 1) + L.kq;  // last step when K is not a multiple of 4: lanes past the end read (0, col) and select a true zero (tail_in)
       pbt[c] = reinterpret_cast<const double*>(lds_b) + (kt < K ? kt : 0) + BP * colc[c];
     }
     // two-stage software pipeline over the k steps: the fragments of step s + 1 are requested before the MFMAs of step s;
     // the scheduling barrier keeps the compiler from hoisting ALL fragment reads of the product to its top (KS x (MA + NC)
     // live doubles: the multi-K kernel then needs 200-260 VGPRs and runs at one or two waves per SIMD)
+    // A's padding columns are zeros, but 0 x Inf is NaN: the lanes past the end of K multiply them by 0.0, not by an element of B
+    const bool tail_in = 4 * (KS - 1) + L.kq < K;
     double av[2][MA], bv[2][NC];
     auto fetch = [&](int s, int buf) {
 #pragma unroll
       for (int a = 0; a < MA; ++a) av[buf][a] = pa[a][s * 4 * AP];
 #pragma unroll
-      for (int c = 0; c < NC; ++c) bv[buf][c] = (s == KS - 1 && (K & 3)) ? pbt[c][0] : pb[c][4 * s];
+      for (int c = 0; c < NC; ++c) bv[buf][c] = (s == KS - 1 && (K & 3)) ? (tail_in ? pbt[c][0] : 0.0) : pb[c][4 * s];
     };
     fetch(0, 0);
 #pragma unroll
@@ -424,12 +426,14 @@ __device__ __forceinline__ void mm_class_stream_body(const Desc* __restrict__ de
       const int kt = 4 * (KS - 1) + L.kq;
       pbt[c] = reinterpret_cast<const double*>(lds_b) + (kt < K ? kt : 0) + BP * colc[c];
     }
+    // A's padding columns are zeros, but 0 x Inf is NaN: the lanes past the end of K multiply them by 0.0, not by an element of B
+    const bool tail_in = 4 * (KS - 1) + L.kq < K;
     double av[2][MA], bv[2][NC];
     auto fetch = [&](int s, int buf) {
 #pragma unroll
       for (int a = 0; a < MA; ++a) av[buf][a] = pa[a][s * 4 * AP];
 #pragma unroll
-      for (int c = 0; c < NC; ++c) bv[buf][c] = (s == KS - 1 && (K & 3)) ? pbt[c][0] : pb[c][4 * s];
+      for (int c = 0; c < NC; ++c) bv[buf][c] = (s == KS - 1 && (K & 3)) ? (tail_in ? pbt[c][0] : 0.0) : pb[c][4 * s];
     };
     fetch(0, 0);
 #pragma unroll

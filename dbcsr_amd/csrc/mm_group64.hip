@@ -212,7 +212,8 @@ mm_numeric_f64_group(const Desc* __restrict__ descs, const Entry* __restrict__ e
   // fragment addresses (image 0 of A; image `bsel` of B)
   const double* pa[MA];
   const double* pb[NC];
-  const double* pbt[NC];  // last k step when S is not a multiple of 4: lanes past the end read element (0, col) (A's padding is zero)
+  const double* pbt[NC];  // last k step when S is not a multiple of 4: lanes past the end read element (0, col) and select 0.0 (A's padding is zero, 0 x Inf is NaN)
+  const bool tail_in = 4 * (KS - 1) + L.kq < S;
 #pragma unroll
   for (int a = 0; a < MA; ++a) {
     int row = 8 * a + L.rowl;
@@ -324,7 +325,7 @@ mm_numeric_f64_group(const Desc* __restrict__ descs, const Entry* __restrict__ e
 #pragma unroll
         for (int a = 0; a < MA; ++a) av[a] = pa[a][par * (A_IMG / 8) + s4 * 4 * S];
 #pragma unroll
-        for (int c = 0; c < NC; ++c) bv[c] = (s4 == KS - 1 && (S & 3)) ? pbtx[c][0] : pbx[c][4 * s4];
+        for (int c = 0; c < NC; ++c) bv[c] = (s4 == KS - 1 && (S & 3)) ? (tail_in ? pbtx[c][0] : 0.0) : pbx[c][4 * s4];
 #pragma unroll
         for (int a = 0; a < MA; ++a)
 #pragma unroll

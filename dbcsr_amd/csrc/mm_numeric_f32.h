@@ -64,13 +64,15 @@ __device__ __forceinline__ void cblock_f32_lds(const Desc& d, const Entry* __res
         }
       }
     if (p + 1 < cnt) issue(p + 1);
-    // multiply: lane (i, kh) feeds A[i][2s + kh] and B[2s + kh][i]; the odd-k tail reads A's zero padding column
+    // multiply: lane (i, kh) feeds A[i][2s + kh] and B[2s + kh][i]; the odd-k tail reads A's zero padding column and multiplies it by a true zero
+    // (0 x Inf is NaN: an Inf in B's last row must not reach the sum a second time as NaN)
     const int nsteps = (ks + 1) >> 1;
     int aoff = arow + m * kh;
     for (int s2 = 0; s2 < nsteps; ++s2) {
       const int kk = 2 * s2 + kh;
       const float av = lds_a[aoff];
-      const float bv = lds_bt[bcol + LDN * (kk < ks ? kk : ks - 1)];
+      const float bl = lds_bt[bcol + LDN * (kk < ks ? kk : ks - 1)];
+      const float bv = kk < ks ? bl : 0.0f;
       aoff += 2 * m;
       acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
     }
@@ -155,7 +157,9 @@ __device__ __forceinline__ void cblock_f32_exact(const Desc& d, const Entry* __r
 #pragma unroll
     for (int s2 = 0; s2 < KS2; ++s2) {
       const float av = pa[s2 * 2 * M];
-      const float bv = (s2 == KS2 - 1) ? pbt[0] : pb[s2 * 2 * LDN];
+      float bv = (s2 == KS2 - 1) ? pbt[0] : pb[s2 * 2 * LDN];
+      if constexpr ((K & 1) != 0)
+        if (s2 == KS2 - 1 && kh) bv = 0.0f;   // the odd-k tail: A's padding column is zero, and so is what it is multiplied by (0 x Inf is NaN)
       acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
     }
     i0 = i1;

@@ -68,8 +68,8 @@ struct TileKernel {
 // pb = slot + lane part of B, every fragment at a compile-time offset from them.  No clamping: a lane whose row (column) is past
 // the block reads the neighbouring element -- finite data of the block, or the slot's padding, which the masked last DMA piece
 // fills with the zeros of its out-of-range bytes -- and only pollutes accumulator rows (columns) that are never stored.  In the
-// last k step of a K that is not a multiple of 4 the lanes past the end get an exact zero on the A side and a finite B value
-// (element (0, col + 1), or the zero padding after the last column).
+// last k step of a K that is not a multiple of 4 the lanes past the end get an exact zero on BOTH sides: what they read of B (element
+// (0, col + 1), or the zero padding after the last column) may be Inf or NaN, and 0 x Inf is NaN.
 template <int M, int N, int K, int RDV>
 __device__ __forceinline__ void tile_frags(int s, const double* pa, const double* pb, bool ktail_dead, double (&av)[3], double (&bv)[3]) {
   typedef TileKernel<M, N, K, RDV> TK;
@@ -87,6 +87,7 @@ __device__ __forceinline__ void tile_frags(int s, const double* pa, const double
       bv[c] = *(const volatile double __attribute__((address_space(3)))*)(pb + 8 * K * c + 4 * s);
     else
       bv[c] = pb[8 * K * c + 4 * s];
+    if (s == TK::KS - 1 && (K & 3)) bv[c] = ktail_dead ? 0.0 : bv[c];
   }
 }
 

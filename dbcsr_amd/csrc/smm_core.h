@@ -107,9 +107,10 @@ __device__ __forceinline__ void block_product_f64(double (&acc)[MA][NC], const d
 // Same product with both operands already staged in LDS: A as an m x k4 column-major
 // block whose columns k..k4-1 (k4 = k rounded up to 4) are EXACT ZEROS, B as stored
 // (k x n column-major).  Lanes whose k index is past the end read A's zero padding and
-// a clamped (valid, finite) B element, so they contribute exact zeros without any
-// select on loaded values -- which lets the operand fetches of step s+1 stay in flight
-// under the MFMAs of step s (two-stage software pipeline).
+// a clamped (valid) B element that a select replaces by 0.0, so they contribute exact
+// zeros whatever that element holds.  The select follows the load, so the two-stage
+// software pipeline keeps its shape; its cost was measured on config 3 only (inside the
+// parent's spread, profiles/special_values.txt), not on the stack kernels.
 template <int MA, int NC, bool BT = false>
 __device__ __forceinline__ void block_product_f64_lds(double (&acc)[MA][NC], const double* lds_a, const double* lds_b, int m,
                                                       int n, int k, const LaneMap& L) {
@@ -135,7 +136,10 @@ __device__ __forceinline__ void block_product_f64_lds(double (&acc)[MA][NC], con
     for (int a = 0; a < MA; ++a) av[a] = lds_a[aoff[a] + s * astep];
     const int bs = 4 * s <= klast ? s * bstep : (BT ? -n * L.kq : -L.kq);  // past the end: element (k = 0, col), always valid
 #pragma unroll
-    for (int c = 0; c < NC; ++c) bv[c] = lds_b[boff[c] + bs];
+    for (int c = 0; c < NC; ++c) {
+      const double v = lds_b[boff[c] + bs];
+      bv[c] = 4 * s <= klast ? v : 0.0;   // a true zero against A's zero padding: the clamped element may be Inf or NaN, and 0 x Inf is NaN
+    }
   };
   auto mma = [&](const double (&av)[MA], const double (&bv)[NC]) {
 #pragma unroll

@@ -64,7 +64,8 @@ __device__ __forceinline__ void smm_stack_exact_body(const int* __restrict__ sta
     for (int c = 0; c < NC; ++c) acc[a][c] = 0.0;
   const double* pa[MA];
   const double* pb[NC];
-  const double* pbt[NC];  // last k step when K is not a multiple of 4: lanes past the end read a valid, finite element (A's padding is zero)
+  const double* pbt[NC];  // last k step when K is not a multiple of 4: lanes past the end read a valid element and select 0.0 (A's padding is zero, 0 x Inf is NaN)
+  const bool tail_in = 4 * ((K + 3) / 4 - 1) + L.kq < K;
 #pragma unroll
   for (int a = 0; a < MA; ++a) {
     int row = 8 * a + L.rowl;
@@ -125,7 +126,7 @@ __device__ __forceinline__ void smm_stack_exact_body(const int* __restrict__ sta
 #pragma unroll
       for (int a = 0; a < MA; ++a) av[buf][a] = pa[a][st * 4 * AP];
 #pragma unroll
-      for (int c = 0; c < NC; ++c) bv[buf][c] = (st == KS - 1 && (K & 3)) ? pbt[c][0] : pb[c][BT ? st * 4 * BP : 4 * st];
+      for (int c = 0; c < NC; ++c) bv[buf][c] = (st == KS - 1 && (K & 3)) ? (tail_in ? pbt[c][0] : 0.0) : pb[c][BT ? st * 4 * BP : 4 * st];
     };
     fetch(0, 0);
 #pragma unroll

@@ -249,7 +249,8 @@ class MultiplyEngine:
     def filtered(self, M, eps, stream=None, in_place=False):
         """M without the blocks whose squared Frobenius norm is below eps^2 (final filter of a multiply): a packed copy, or with
         in_place=True a matrix that shares M.data and has new row_p / col_i / blk_p (kept blocks stay where they are, nze counts
-        them; cropped(result) packs it).  M itself when nothing falls below eps."""
+        them; cropped(result) packs it).  M itself when nothing falls below eps.  The rule is the drop, as in the reference: a block whose norm
+        is NaN is not below eps and stays (a NaN in a product does not vanish with its block); so does a block whose norm is Inf."""
         st = StreamHandle(stream)
         dev = M.row_p.device
         src = M.desc()

@@ -126,7 +126,7 @@ def test_standalone_filter_both_forms(case, q, dtype):
     if q is None:
         assert X is P and Y is P and P.packed
         return
-    keep = block_sq_norms(hp) >= eps * eps        # the expected pattern, from the downloaded product itself
+    keep = ~(block_sq_norms(hp) < eps * eps)      # the expected pattern, from the downloaded product itself
     assert 0 < np.count_nonzero(keep) < hp.nblks
     hx, hy = check_unpacked_pair(X, Y, P)
     want_row_p = np.concatenate([[0], np.cumsum(np.bincount(hp.rows()[keep], minlength=hp.nbr))])
