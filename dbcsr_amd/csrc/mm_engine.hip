@@ -64,6 +64,7 @@
 #include "mm_aux.h"
 #include "mm_algebra.h"   // add, add_on_diag, trace, dot, norm: the operations between multiplies
 #include "mm_multivec.h"  // the matrix times several dense vectors
+#include "mm_rank_update.h"  // the rank-k update on the stored pattern
 // The library comes in two builds (Makefile): the SHIPPING one holds what a multiply can run by itself -- the kernels listed above, their
 // symbolic phases, plan reuse -- and the LAB one (-DDBCSR_AMD_EXPERIMENTS, libdbcsr_acc_amd_lab.so) adds every dataflow and variant that
 // was built, made parity-green and measured but does not win: the LDS-DMA ring kernels (mm_dma.h), XCD-wide C tiles (mm_tile.*), CU-wide

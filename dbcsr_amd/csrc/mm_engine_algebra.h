@@ -1,7 +1,7 @@
 // mm_engine_algebra.h -- part of mm_engine.hip (included inside extern "C", after mm_engine_ops.h): the C-ABI operations between multiplies --
 // dbcsr_amd_bcsr_add_count / _add_apply, the pieces of dbcsr_add_on_diag (dbcsr_amd_bcsr_diag_count / _diag_fill / _diag_shift), dbcsr_amd_bcsr_trace,
-// _dot, _norm2, and the norms and vectors: dbcsr_amd_bcsr_maxabs, _row_sums, _col_sums, _gershgorin, _get_diag, _set_diag, _scale_by_vector, _matvec, _multivec.
-// Kernels: mm_algebra.h, mm_multivec.h.  The reductions, the diagonal pieces, the same-pattern add and the norms and vectors use buffers of their own (Engine::alg_*) and the
+// _dot, _norm2, and the norms and vectors: dbcsr_amd_bcsr_maxabs, _row_sums, _col_sums, _gershgorin, _get_diag, _set_diag, _scale_by_vector, _matvec, _multivec, _rank_update.
+// Kernels: mm_algebra.h, mm_multivec.h, mm_rank_update.h. The reductions, the diagonal pieces, the same-pattern add and the norms and vectors use buffers of their own (Engine::alg_*) and the
 // scan's scratch, which no saved plan depends on (the checksum uses it the same way): they do NOT invalidate the plan.  The union add borrows the
 // symbolic phase's bitmaps and prefix arrays and invalidates it, as filter and crop do.
 #ifndef DBCSR_AMD_MM_ENGINE_ALGEBRA_H
@@ -681,6 +681,51 @@ int dbcsr_amd_bcsr_multivec(void* handle, libsmm_acc_data_t datatype, char trans
   const int64_t* total = trans == 'N' ? roff + a->nblkrows : coff + a->nblkcols;   // the full rows of op(A)
   DBCSR_AMD_BY_TYPE(multivec_launch, E, st, a, rp, cp, S_r, S_c, roff, coff, total, alpha, beta, mode, nrhs, x, n_x, ldx, y, n_y, ldy);
   return check(hipGetLastError(), "dbcsr_amd_bcsr_multivec", __FILE__, __LINE__);
+}
+
+// ---- rank-k update on the stored pattern (kernels: mm_rank_update.h) ------------------------------------------------------------------------------------
+extern "C++" {
+// 16-byte loads of a row-by-row tensor: its first element and every row start on a 16-byte boundary
+template <typename T>
+static inline int rank_update_vec_ok(const void* p, int64_t ld) {
+  return aligned16(p) && (ld * (int64_t)sizeof(T)) % 16 == 0 ? 1 : 0;
+}
+
+template <typename T>
+static void rank_update_launch(hipStream_t st, dbcsr_amd_bcsr* a, const int64_t* roff, const int64_t* coff, int conj, const double alpha[2],
+                               const double beta[2], int mode, int nrhs, const void* x, int64_t n_x, int64_t ldx, const void* y, int64_t n_y, int64_t ldy) {
+  using Acc = typename MatvecAcc<T>::type;
+  const int nbr = a->nblkrows, S = algebra_split(nbr, a->nblks), beta_zero = (mode & kMatvecBetaZero) ? 1 : 0;
+  if (mode & kMatvecNoProduct)
+    hipLaunchKernelGGL((algebra_rank_update_scale<T>), grid_for((int64_t)nbr * S * 64), dim3(256), 0, st, a->row_p, a->col_i, a->blk_p,
+                       static_cast<T*>(a->data), a->row_blk_size, a->col_blk_size, roff, coff, nbr, S, beta_zero, n_x, n_y, algebra_scalar<T>(beta));
+  else
+    hipLaunchKernelGGL((algebra_rank_update_blocks<T>), grid_for((int64_t)nbr * S * 64), dim3(256), 0, st, a->row_p, a->col_i, a->blk_p,
+                       static_cast<T*>(a->data), a->row_blk_size, a->col_blk_size, roff, coff, nbr, S, conj, beta_zero, static_cast<const T*>(x), n_x, ldx,
+                       rank_update_vec_ok<T>(x, ldx), static_cast<const T*>(y), n_y, ldy, rank_update_vec_ok<T>(y, ldy), nrhs, algebra_scalar<Acc>(alpha),
+                       algebra_scalar<Acc>(beta));
+}
+}  // extern "C++"
+
+int dbcsr_amd_bcsr_rank_update(void* handle, libsmm_acc_data_t datatype, char trans, const double alpha[2], int nrhs, const void* x, int64_t n_x,
+                               int64_t ldx, const void* y, int64_t n_y, int64_t ldy, const double beta[2], dbcsr_amd_bcsr* a, void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E || !alpha || !a || !beta || n_x < 0 || n_y < 0 || nrhs < 0 || ldx < nrhs || ldy < nrhs) return -1;
+  if (trans != 'T' && trans != 'C') return -1;
+  if (!algebra_type(datatype)) return -10;
+  const bool zc = datatype == dbcsr_type_complex_8;
+  const bool alpha_zero = alpha[0] == 0.0 && (!zc || alpha[1] == 0.0), beta_zero = beta[0] == 0.0 && (!zc || beta[1] == 0.0);
+  const bool product = !alpha_zero && nrhs > 0;   // alpha == 0 or no column: X and Y are not read, A <- beta A
+  if (product && ((n_x > 0 && !x) || (n_y > 0 && !y))) return -1;
+  hipStream_t st = stream_of(stream);
+  if (a->nblkrows == 0 || a->nblkcols == 0 || a->nblks == 0) return 0;   // an empty matrix: nothing to write
+  if (n_x == 0 || n_y == 0) return 0;                                      // (no element has both its rows)
+  if (!product && algebra_is_one(datatype, beta)) return 0;               // A <- A: nothing is launched
+  const int mode = (product ? 0 : kMatvecNoProduct) | (beta_zero ? kMatvecBetaZero : 0);
+  const int64_t *roff = nullptr, *coff = nullptr;
+  if (vector_offsets(E, st, a, &roff, &coff)) return -1;
+  DBCSR_AMD_BY_TYPE(rank_update_launch, st, a, roff, coff, zc && trans == 'C' ? 1 : 0, alpha, beta, mode, nrhs, x, n_x, ldx, y, n_y, ldy);
+  return check(hipGetLastError(), "dbcsr_amd_bcsr_rank_update", __FILE__, __LINE__);
 }
 #undef DBCSR_AMD_BY_TYPE
 

@@ -14,6 +14,7 @@
     dbcsr_scale_by_vector(matrix, alpha, side)                  A <- A*diag(alpha) ("right") or diag(alpha)*A ("left")
     dbcsr_matvec(matrix, vec_in, vec_out, alpha, beta, trans)   y <- alpha*op(A)*x + beta*y with dense device vectors (not a mirror, see there)
     dbcsr_multivec(matrix, vecs_in, vecs_out, alpha, beta, trans)  Y <- alpha*op(A)*X + beta*Y with nrhs dense device vectors at once: A is read once
+    dbcsr_rank_update(matrix, vecs_x, vecs_y, alpha, beta, trans)  A_IJ <- beta*A_IJ + alpha*X_I*op(Y_J) on the stored blocks only (not a mirror, see there)
 
 Same argument names and error behaviour; the work is done by the C-ABI engine (include/dbcsr_amd_mm.h, "Matrix algebra between
 multiplies") on the GPU, for float64, float32 and complex128 data.  One rank / one device here: of a distributed matrix trace, dot
@@ -459,3 +460,64 @@ def dbcsr_multivec(matrix, vecs_in, vecs_out=None, alpha=1.0, beta=0.0, trans="N
     if rc != 0:
         raise RuntimeError("dbcsr_amd_bcsr_multivec failed (%d)" % rc)
     return vecs_out
+
+
+def _overlaps(t, n, ld, nrhs, data):
+    """the element range of an (n, nrhs) tensor with row stride ld intersects the range of a data area"""
+    if not n or not nrhs or not data.numel():
+        return False
+    t0, d0 = t.data_ptr(), data.data_ptr()
+    return t0 < d0 + data.numel() * data.element_size() and d0 < t0 + t.element_size() * ((n - 1) * ld + nrhs)
+
+
+def dbcsr_rank_update(matrix, vecs_x, vecs_y=None, alpha=1.0, beta=1.0, trans="T", engine=None, stream=None):
+    """A_IJ <- beta * A_IJ + alpha * X_I * op(Y_J) for every stored block (I, J), in place, and nothing else: the rank-nrhs update restricted to the pattern
+    the matrix has -- the density matrix P = C C^T on the pattern of S, energy-weighted density matrices, low-rank corrections, outer products of Lanczos /
+    LOBPCG blocks.  NOT a mirror of a routine of the reference: it serves the call CP2K makes as cp_dbcsr_plus_fm_fm_t with keep_sparsity, with dense
+    device tensors in place of full matrices, and does not claim that name.  op is the transpose (trans "T") or the conjugate transpose ("C"; real data:
+    "T").  vecs_x is (full rows, nrhs), vecs_y (full columns, nrhs): 2-D device tensors of the matrix' data type in dbcsr_multivec's layout (stride(1) == 1,
+    stride(0) >= nrhs: a contiguous tensor or a column slice of a wider basis); X_I are the rows of vecs_x of block row I, Y_J the rows of vecs_y of block
+    column J.  vecs_y=None: Y is X (the matrix must have equal row and column block sizes).  The pattern never changes: no index array is written,
+    index_stamp() stays, a multiply with the matrix as operand afterwards reuses its plan; the holes of an unpacked matrix keep their bits.  Products and sums
+    in double / complex double, alpha and beta applied in double, one rounding per element, the same bits on every call.  beta == 0: the matrix' values are
+    not read; alpha == 0 or nrhs == 0: X and Y are not read and A <- beta * A in the data's own precision; alpha == 0 and beta == 1: nothing is launched.
+    Symmetry 'N': any X, Y.  'S': vecs_y must be None and op the transpose; 'H': vecs_y must be None, trans "C", alpha and beta real -- the stored triangle
+    is then updated block by block, which is the update of the full symmetric / hermitian matrix.  'A' and 'K': ValueError.  X and Y are only read: they
+    may be the same tensor or overlap each other, but neither may overlap matrix.data (ValueError).  Asynchronous on the stream; returns None."""
+    name = "dbcsr_rank_update"
+    sym = _check_symmetry(name, matrix)
+    if trans not in ("T", "C"):
+        raise ValueError("%s: trans must be 'T' or 'C', got %r" % (name, trans))
+    matrix.dtype_code
+    if not matrix.dtype.is_complex:
+        trans = "T"   # (real data: the conjugate transpose is the transpose)
+    _check_scalar(name, matrix, alpha, beta)
+    if sym != "N":
+        if sym in ("A", "K"):
+            raise ValueError("%s: not defined for an antisymmetric / antihermitian matrix (symmetry %r)" % (name, sym))
+        matrix.symmetry_kind()   # (which symmetries go with which data)
+        _check_square(name, matrix)
+        if vecs_y is not None:
+            raise ValueError("%s: a matrix with symmetry %r takes X alone (vecs_y=None): X op(Y) would not keep the symmetry" % (name, sym))
+        if sym == "S" and trans != "T":
+            raise ValueError("%s: a symmetric matrix takes trans 'T' (X X^H is not symmetric)" % name)
+        if sym == "H" and (trans != "C" or complex(alpha).imag != 0 or complex(beta).imag != 0):
+            raise ValueError("%s: a hermitian matrix takes trans 'C' and real alpha and beta" % name)
+    n_rows, n_cols = _full_size(matrix.row_blk_size), _full_size(matrix.col_blk_size)
+    nrhs, ldx = _check_vectors(name, matrix, vecs_x, n_rows)
+    if vecs_y is None:
+        _check_square(name, matrix)
+        vecs_y, ldy = vecs_x, ldx
+    else:
+        ny, ldy = _check_vectors(name, matrix, vecs_y, n_cols)
+        if ny != nrhs:
+            raise ValueError("%s: vecs_x has %d columns, vecs_y %d" % (name, nrhs, ny))
+    if _overlaps(vecs_x, n_rows, ldx, nrhs, matrix.data) or _overlaps(vecs_y, n_cols, ldy, nrhs, matrix.data):
+        raise ValueError("%s: vecs_x / vecs_y overlap the matrix' data area" % name)
+    E = engine or default_engine()
+    st = StreamHandle(stream)
+    d = matrix.desc()   # (only the data area is written)
+    rc = E.L.dbcsr_amd_bcsr_rank_update(E.h, matrix.dtype_code, trans.encode(), _z(alpha), nrhs, vecs_x.data_ptr() if n_rows and nrhs else None, n_rows, ldx,
+                                        vecs_y.data_ptr() if n_cols and nrhs else None, n_cols, ldy, _z(beta), C.byref(d), st.ptr)
+    if rc != 0:
+        raise RuntimeError("dbcsr_amd_bcsr_rank_update failed (%d)" % rc)

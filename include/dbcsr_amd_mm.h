@@ -403,6 +403,25 @@ int dbcsr_amd_bcsr_matvec(void* handle, libsmm_acc_data_t datatype, char trans, 
 int dbcsr_amd_bcsr_multivec(void* handle, libsmm_acc_data_t datatype, char trans, const double alpha[2], const dbcsr_amd_bcsr* a,
   int kind /* -1; 0 ... 3: S A H K */, int nrhs, const void* x, int64_t n_x, int64_t ldx, const double beta[2], void* y, int64_t n_y, int64_t ldy,
   void* stream);
+/*   _rank_update  A_IJ <- beta A_IJ + alpha X_I op(Y_J) for every block (I, J) the index of A names, in place, and nothing else: the pattern never
+ *               changes, no index array is written (what cp_dbcsr_plus_fm_fm_t with keep_sparsity does).  op: trans 'T' (transpose) or 'C' (conjugate
+ *               transpose; real data: 'T'), any other: -1.  X is n_x x nrhs, Y is n_y x nrhs, dense DEVICE matrices of the matrix' data type in
+ *               _multivec's layout (row by row, element (i, v) at i ld + v, ld >= nrhs); X_I are the rows of X of block row I, Y_J the rows of Y of
+ *               block column J.  y == x is legal, and so is any overlap of the two: both are only read; neither may overlap A's data area.  Products
+ *               and sums in double / complex double (fp32 data converted first: its products are exact), alpha and beta applied in double, one
+ *               rounding to the data's type per element; every element has one owner: no floating-point atomics, the same bits on every call.
+ *               beta == 0: A's values are not read (a NaN in A does not reach the result).  alpha == 0 or nrhs == 0: X and Y are not read,
+ *               A <- beta A in the data's own precision; with beta == 1 as well nothing is launched.  It goes by the index, never by the extent of
+ *               the data area: the holes of an unpacked matrix keep their bits.  A stored triangle is updated block by block like any other matrix;
+ *               which X, Y, trans and scalars keep its symmetry is the caller's business (Python: dbcsr_rank_update).  Buffers of its own, a saved
+ *               plan stays; asynchronous, no synchronisation.  -1 for a null handle, matrix or scalar, a bad trans, nrhs < 0, n_x < 0 or n_y < 0,
+ *               ldx < nrhs or ldy < nrhs, and a null x / y when they would be read (alpha != 0, nrhs > 0 and rows to read); -10 for a data type the
+ *               algebra does not know; 0 with nothing written for an empty matrix.  Every read of X stays in rows below n_x and columns below nrhs,
+ *               every read of Y in rows below n_y and columns below nrhs: rows outside a block, rows behind the tensors and padding columns are never
+ *               loaded, they enter as true zeros.  An element of A whose row of X or of Y would lie at or behind n_x / n_y is not written at all; every
+ *               write stays inside the blocks that the index names. */
+int dbcsr_amd_bcsr_rank_update(void* handle, libsmm_acc_data_t datatype, char trans, const double alpha[2], int nrhs, const void* x, int64_t n_x,
+  int64_t ldx, const void* y, int64_t n_y, int64_t ldy, const double beta[2], dbcsr_amd_bcsr* a, void* stream);
 
 /* Measurement helper (bench.py, roofline.fabric): what the L2 <-> Infinity-Cache fabric of the current device delivers, in TB/s -- a
  * plain streaming read of a 160 MB window by all CUs, and the block gather of the block-product dataflow (4232-byte blocks from

@@ -46,6 +46,15 @@ S with the volume of the partial matrices:
 With DBCSR_AMD_LAB=1 it also times multivec.N at 32 and 64 through an engine with DBCSR_AMD_MULTIVEC_WAVES=1 (rows ind.N: independent waves, every
 tile of 16 right-hand sides loads the block itself, against the shared staging of what ships).
 
+With --rank-update only the rank-k update on the stored pattern is timed (dbcsr_amd_bcsr_rank_update, kernels of dbcsr_amd/csrc/mm_rank_update.h),
+alternating with its yardsticks: scale (dbcsr_amd_bcsr_scale_window of the whole matrix: A read and written once, the same traffic), norm (one read of A),
+rank(k) = A <- 0.5 A + 1e-3 X Y^T at nrhs 1, 4, 16, 64, 256 and rank.xx(64) with Y = X (the same pointer).  X and Y are contiguous (n, k) tensors of
+ones (ld = k; a run stops when the self-check -- alpha = 1, beta = 0 gives nrhs in every element -- fails).  The report has rank(k) / scale, 2 nze nrhs / time in TFLOP/s -- and, with --mfma-tflops T (the fp64 MFMA figure bench.py --full
+measured in the same session: roofline.achieved of its block-product kernel), the fraction of T -- and the condition rank(k) < k * rank(1) for k = 4, 16, 64
+in every alternation:
+
+    python tools/ops_bench.py --rank-update --alternations 7 --warmup 2 --mfma-tflops T --out profiles/rank_update.txt
+
 A sample is `--reps` calls back to back between two device events, divided by reps.  Bytes are counted from the shapes: 8 * (elements read + elements
 written) of the data areas, index arrays left out.  Spread = (max - min) / median over the samples."""
 import argparse
@@ -220,6 +229,79 @@ def multivec(args, say, lines, rng, b, nb, st):
             f.write("\n".join(lines) + "\n")
 
 
+def rank_update(args, say, lines, rng, b, nb, st):
+    E = MultiplyEngine()
+    A = matrix_of(rng.random((nb, nb)) < args.fill_flat, b, 1)
+    a = A.desc()
+    f64 = L.dbcsr_type_real_8
+    n = nb * b
+    kmax = 256
+    alpha, beta, zero, one = (C.c_double * 2)(1e-3, 0.0), (C.c_double * 2)(0.5, 0.0), (C.c_double * 2)(0.0, 0.0), (C.c_double * 2)(1.0, 0.0)
+    out2 = (C.c_double * 2)()
+    X = torch.ones(n * kmax, dtype=torch.float64, device="cuda")
+    Y = torch.ones(n * kmax, dtype=torch.float64, device="cuda")
+    check = lambda rc: rc == 0 or sys.exit("a library call failed (%d)" % rc)
+
+    def ru(k, y, al=alpha, be=beta):
+        # (the first n k elements of the tensors of ones as a contiguous (n, k) tensor: ld = k)
+        return lambda: check(E.L.dbcsr_amd_bcsr_rank_update(E.h, f64, b"T", al, k, X.data_ptr(), n, k, y.data_ptr(), n, k, be, C.byref(a), st.ptr))
+
+    run = {
+        "scale": lambda: check(E.L.dbcsr_amd_bcsr_scale_window(E.h, f64, C.byref(a), 0.9999, -1, -1, -1, -1, st.ptr)),
+        "norm": lambda: check(E.L.dbcsr_amd_bcsr_norm2(E.h, f64, C.byref(a), 0, out2, st.ptr)),
+    }
+    width = {}
+    for k in (1, 4, 16, 64, 256):
+        run["rank.%d" % k] = ru(k, Y)
+        width["rank.%d" % k] = k
+    run["rank.xx.64"] = ru(64, X)
+    width["rank.xx.64"] = 64
+    # X and Y of ones, beta = 0, alpha = 1: every stored element is nrhs
+    keep = A.data.clone()
+    ru(64, Y, one, zero)()
+    torch.cuda.synchronize()
+    right = bool((A.data == 64.0).all().item())
+    say("rank.64 with alpha = 1, beta = 0 on tensors of ones: every element of A is 64: %s" % right)
+    if not right:
+        sys.exit("the rank-k update is wrong: nothing is timed")
+    A.data.copy_(keep)
+    del keep
+    times = {k: [] for k in run}
+    for step in range(args.warmup + args.alternations):
+        for k in run:
+            t = sample(run[k], args.reps)
+            if step >= args.warmup:
+                times[k].append(t)
+    say("")
+    say("A: %d blocks, %.1f MB" % (A.nblks, 8e-6 * A.nze))
+    med = {}
+    for k in run:
+        v = sorted(times[k])
+        med[k] = v[len(v) // 2]
+        nbytes = (8 if k == "norm" else 16) * A.nze
+        say("  %-11s  median %8.4f ms  min %8.4f  max %8.4f  spread %5.1f %%  %8.1f GB/s of A   samples: %s"
+            % (k, med[k], v[0], v[-1], 100 * (v[-1] - v[0]) / med[k], 1e-6 * nbytes / med[k], " ".join("%.4f" % x for x in times[k])))
+    say("")
+    say("time against dbcsr_scale (median / median; the ratio per alternation, sample by sample), and 2 nze nrhs / time"
+        + (" against %.1f TFLOP/s" % args.mfma_tflops if args.mfma_tflops else ""))
+    for k in width:
+        r = sorted(x / z for x, z in zip(times[k], times["scale"]))
+        tf = 2e-9 * A.nze * width[k] / med[k]
+        say("  %-11s / scale  %6.2f   (per alternation %.2f ... %.2f)   %7.2f TFLOP/s%s"
+            % (k, med[k] / med["scale"], r[0], r[-1], tf, "   %.3f of the measured MFMA figure" % (tf / args.mfma_tflops) if args.mfma_tflops else ""))
+    say("")
+    say("condition: rank(k) below k * rank(1) in every alternation, k = 4, 16, 64")
+    ok = True
+    for k in (4, 16, 64):
+        r = sorted(x / (k * z) for x, z in zip(times["rank.%d" % k], times["rank.1"]))
+        ok = ok and r[-1] < 1.0
+        say("  rank.%-3d / (%2d * rank.1)  %.3f ... %.3f   %s" % (k, k, r[0], r[-1], "holds" if r[-1] < 1.0 else "FAILS"))
+    say("  the condition %s" % ("holds" if ok else "FAILS"))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=32768)
@@ -232,6 +314,8 @@ def main():
     ap.add_argument("--colsums", action="store_true", help="the forms of algebra_col_sums against each other (lab build)")
     ap.add_argument("--matvec", action="store_true", help="only the matrix-vector product, its yardsticks and the sums its passes are made from")
     ap.add_argument("--multivec", action="store_true", help="only the matrix times several dense vectors and its yardsticks")
+    ap.add_argument("--rank-update", action="store_true", help="only the rank-k update on the stored pattern and its yardsticks")
+    ap.add_argument("--mfma-tflops", type=float, default=None, help="with --rank-update: the fp64 MFMA figure bench.py --full measured in the same session")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "ops_bench.py measures on the GPU"
@@ -247,6 +331,8 @@ def main():
         return colsums(args, say, lines, rng, b, nb, st)
     if args.multivec:
         return multivec(args, say, lines, rng, b, nb, st)
+    if args.rank_update:
+        return rank_update(args, say, lines, rng, b, nb, st)
     only = ("norm", "norm.T", "matvec.N", "matvec.T", "matvec.S", "gersh.N", "colnorm", "gersh.S") if args.matvec else None
     # the same-pattern pair
     mask = rng.random((nb, nb)) < args.fill_flat
