@@ -10,26 +10,17 @@
 // All of them stream memory: 16-byte accesses where the addresses allow (a block of a matrix with 1 x 1 or odd blocks starts at any element), enough waves
 // per block row (row_split) to fill the chip, no atomics on data, no floating-point atomics at all -- the reductions write one partial per wave and
 // checksum_final (mm_aux.h) sums the partials in a fixed order, so a result is the same bits on every call.
+// Every kernel that goes through a block element by element does it with walk_block / walk_block_values (mm_block_walk.h: the head in front of the
+// first 16-byte boundary, the whole packs, the tail, in one fixed order per thread); the row passes (row_sum_slots, matvec_row_slots) walk slots at a
+// stride instead and share their geometry, their dispatch on the block's shift and their hand-over (row_slots_of, DBCSR_AMD_BY_SHIFT, row_handover), the column
+// passes the rotated add of a lane's run (add_run_rotated).
 #ifndef DBCSR_AMD_MM_ALGEBRA_H
 #define DBCSR_AMD_MM_ALGEBRA_H
+#include "mm_block_walk.h"  // Pack16, Pack16U, walk_block
 #include "mm_complex.h"
 #include "mm_epilogue.h"  // wave_sum
 
 namespace dbcsr_amd {
-
-// 16 bytes of elements: what a lane moves per access where the addresses allow
-template <typename T>
-struct alignas(16) Pack16 {
-  static constexpr int V = 16 / (int)sizeof(T);
-  T v[V];
-};
-
-// ... the same 16 bytes at an address that is only element-aligned: a source block whose start is not congruent to its destination's modulo 16 bytes
-// (blocks of 23 x 23 doubles start at odd elements half of the time) is still read 16 bytes per lane, as one unaligned access or two halves
-template <typename T>
-struct alignas(alignof(T) < 16 ? alignof(T) : 16) Pack16U {
-  T v[Pack16<T>::V];
-};
 
 // bits of `mode`: the scalar is exactly 1 and the operand is taken as it is (bit-identical, NaN and -0 included)
 constexpr int kAlphaIsOne = 1, kBetaIsOne = 2;
@@ -52,13 +43,6 @@ __device__ __forceinline__ double re_of(z64 x) { return x.re; }
 __device__ __forceinline__ double im_of(double) { return 0.0; }
 __device__ __forceinline__ double im_of(float) { return 0.0; }
 __device__ __forceinline__ double im_of(z64 x) { return x.im; }
-
-// elements in front of the first 16-byte boundary of a block that starts at element `off` of a 16-byte aligned area
-template <typename T>
-__device__ __forceinline__ int head_of(int64_t off) {
-  constexpr int V = Pack16<T>::V;
-  return (int)((V - (off & (V - 1))) & (V - 1));
-}
 
 // ---- same pattern? ---------------------------------------------------------------------------------------------------
 // S waves per block row of A (both matrices have nblks blocks: the host checked).  flags: bit 0 row_p or col_i differ, bit 1 blk_p differs,
@@ -154,34 +138,23 @@ algebra_add_blocks(const int* __restrict__ row_p, const int* __restrict__ col_i,
       else if (have == 1) d[e] = scaled_by(a[e], alpha, mode & kAlphaIsOne);
       else d[e] = scaled_by(b[e], beta, mode & kBetaIsOne);
     };
-    if (V == 1 || !vec_ok) {
-      for (int e = lane; e < ne; e += 64) one(e);
-      continue;
-    }
-    const int h = head_of<T>(dof), head = h < ne ? h : ne, nv = (ne - head) / V;
-    if (lane < head) one(lane);
-    const Pack16U<T>* av = reinterpret_cast<const Pack16U<T>*>(a + head);
-    const Pack16U<T>* bv = reinterpret_cast<const Pack16U<T>*>(b + head);
-    Pack16<T>* dv = reinterpret_cast<Pack16<T>*>(d + head);
-    for (int q = lane; q < nv; q += 64) {
+    walk_block<T>(dof, ne, lane, 64, vec_ok, one, [&](int e) {   // (aligned on dst's block)
       Pack16<T> r;
       if (have == 3) {
-        const Pack16U<T> x = av[q], y = bv[q];
+        const Pack16U<T> x = *reinterpret_cast<const Pack16U<T>*>(a + e), y = *reinterpret_cast<const Pack16U<T>*>(b + e);
 #pragma unroll
         for (int u = 0; u < V; ++u) r.v[u] = axpby(x.v[u], y.v[u], alpha, beta, mode);
       } else if (have == 1) {
-        const Pack16U<T> x = av[q];
+        const Pack16U<T> x = *reinterpret_cast<const Pack16U<T>*>(a + e);
 #pragma unroll
         for (int u = 0; u < V; ++u) r.v[u] = scaled_by(x.v[u], alpha, mode & kAlphaIsOne);
       } else {
-        const Pack16U<T> y = bv[q];
+        const Pack16U<T> y = *reinterpret_cast<const Pack16U<T>*>(b + e);
 #pragma unroll
         for (int u = 0; u < V; ++u) r.v[u] = scaled_by(y.v[u], beta, mode & kBetaIsOne);
       }
-      dv[q] = r;
-    }
-    const int done = head + nv * V;
-    if (done + lane < ne) one(done + lane);
+      *reinterpret_cast<Pack16<T>*>(d + e) = r;
+    });
   }
 }
 
@@ -310,7 +283,6 @@ template <typename T>
 __global__ void __launch_bounds__(256) algebra_norm2(const int* __restrict__ row_p, const int* __restrict__ col_i, const int64_t* __restrict__ blk_p,
                                                      const T* __restrict__ data, const int* __restrict__ rs, const int* __restrict__ cs, int nbr, int S,
                                                      int symmetric, int vec_ok, double* __restrict__ partials) {
-  constexpr int V = Pack16<T>::V;
   const int lane = threadIdx.x & 63;
   const int64_t wv = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int row = (int)(wv / S), sub = (int)(wv % S);
@@ -320,21 +292,8 @@ __global__ void __launch_bounds__(256) algebra_norm2(const int* __restrict__ row
   for (int b = row_p[row] + sub; b < row_p[row + 1]; b += S) {
     const int c = col_i[b], ne = m * cs[c];
     const int64_t off = blk_p[b];
-    const T* d = data + off;
     double s = 0.0;
-    if (V > 1 && vec_ok) {
-      const int h = head_of<T>(off), head = h < ne ? h : ne, nv = (ne - head) / V, done = head + nv * V;
-      if (lane < head) s += abs2_of(d[lane]);
-      const Pack16<T>* dv = reinterpret_cast<const Pack16<T>*>(d + head);
-      for (int q = lane; q < nv; q += 64) {
-        const Pack16<T> x = dv[q];
-#pragma unroll
-        for (int u = 0; u < V; ++u) s += abs2_of(x.v[u]);
-      }
-      if (done + lane < ne) s += abs2_of(d[done + lane]);
-    } else {
-      for (int e = lane; e < ne; e += 64) s += abs2_of(d[e]);
-    }
+    walk_block_values(data + off, off, ne, lane, 64, vec_ok, [&](int, T x) { s += abs2_of(x); });
     acc += (symmetric && c != row) ? 2.0 * s : s;
   }
   acc = wave_sum(acc);
@@ -372,22 +331,14 @@ algebra_dot(const int* __restrict__ a_row_p, const int* __restrict__ a_col_i, co
     const T* x = a_data + ao;
     const T* y = b_data + bo;
     double s = 0.0;
-    const int h = head_of<T>(ao);
-    if (V > 1 && vec_ok) {   // (aligned on A's block; B's is read from wherever it starts)
-      const int head = h < ne ? h : ne, nv = (ne - head) / V, done = head + nv * V;
-      if (lane < head) s += (double)x[lane] * (double)y[lane];
-      const Pack16<T>* xv = reinterpret_cast<const Pack16<T>*>(x + head);
-      const Pack16U<T>* yv = reinterpret_cast<const Pack16U<T>*>(y + head);
-      for (int q = lane; q < nv; q += 64) {
-        const Pack16<T> p = xv[q];
-        const Pack16U<T> r = yv[q];
+    walk_block<T>(   // (aligned on A's block; B's is read from wherever it starts)
+        ao, ne, lane, 64, vec_ok, [&](int e) { s += (double)x[e] * (double)y[e]; },
+        [&](int e) {
+          const Pack16<T> p = *reinterpret_cast<const Pack16<T>*>(x + e);
+          const Pack16U<T> r = *reinterpret_cast<const Pack16U<T>*>(y + e);
 #pragma unroll
-        for (int u = 0; u < V; ++u) s += (double)p.v[u] * (double)r.v[u];
-      }
-      if (done + lane < ne) s += (double)x[done + lane] * (double)y[done + lane];
-    } else {
-      for (int e = lane; e < ne; e += 64) s += (double)x[e] * (double)y[e];
-    }
+          for (int u = 0; u < V; ++u) s += (double)p.v[u] * (double)r.v[u];
+        });
     acc += (symmetric && c != row) ? 2.0 * s : s;
   }
   acc = wave_sum(acc);
@@ -419,6 +370,58 @@ __device__ __forceinline__ void wave_lds_handover() {
 __device__ __forceinline__ double max_or_nan(double a, double b) { return b != b ? b : (a < b ? b : a); }
 
 constexpr int kStageElems = 1024;   // doubles of LDS per wave (column sums: one piece of a block; row sums: the lanes' accumulators at the end of a row)
+
+// ---- what the row passes share (algebra_row_sums, algebra_matvec_rows) ---------------------------------------------------------------------------------
+// The 16-byte slots of a block row with m element rows: p = m / gcd(V, m) lanes are one period of the element rows, P = the largest multiple of p that 64
+// lanes hold (0 when p > 64: the slot form is not used)
+struct RowSlots {
+  int p, P;
+};
+template <int V>
+__device__ __forceinline__ RowSlots row_slots_of(int m) {
+  const int g = V == 1 ? 1 : (m % V == 0 ? V : (m % 2 == 0 ? 2 : 1));   // gcd(V, m), V = 1, 2 or 4
+  const int p = m / g;
+  return RowSlots{p, (64 / p) * p};
+}
+
+// F<T, A>(...) for the wave-uniform shift a = 0 ... V - 1 of a block against a 16-byte boundary, A the same value as a compile-time constant (T and V: the
+// caller's; 1 % V ... keep a type with a smaller V from instantiating a shift it does not have).  A macro, so that the calls stand in the kernel as they
+// would by hand: through a function that takes a callable the compiler laid the branches of algebra_matvec_rows<double> out differently, a product and
+// its sum ended up in different blocks and were no longer contracted -- other bits.
+#define DBCSR_AMD_BY_SHIFT(F, a, ...)               \
+  do {                                              \
+    if (V == 1 || (a) == 0) F<T, 0>(__VA_ARGS__);   \
+    else if ((a) == 1) F<T, 1 % V>(__VA_ARGS__);    \
+    else if ((a) == 2) F<T, 2 % V>(__VA_ARGS__);    \
+    else F<T, 3 % V>(__VA_ARGS__);                  \
+  } while (0)
+
+// The end of a block row: the 2 V - 1 accumulators of every lane go through the wave's LDS slice (64 per accumulator), and lane r = lane, lane + 64, ...
+// below m hands store(r, sum) the sum of those that belong to element row r -- accumulator k of lane l belongs to row (V l + k - (V - 1)) mod m -- in the
+// order (k, then l = l0, l0 + p, ... below P).
+template <int V, typename Acc, typename Store>
+__device__ __forceinline__ void row_handover(const Acc (&acc)[2 * V - 1], Acc* slice, int lane, int m, RowSlots sl, Store&& store) {
+  constexpr int K = 2 * V - 1;
+#pragma unroll
+  for (int k = 0; k < K; ++k) slice[k * 64 + lane] = acc[k];
+  wave_lds_handover();   // (the slice is this wave's alone)
+  for (int r = lane; r < m; r += 64) {
+    Acc sum = Acc(0.0);
+    for (int k = 0; k < K; ++k) {
+      // the lanes l with (V l + k - (V - 1)) mod m == r: the first one below the period p (found without touching LDS), then every p-th
+      int cur = ((k - (V - 1)) % m + m) % m, l0 = 0;
+      while (l0 < sl.p && cur != r) {
+        ++l0;
+        cur += V;
+        if (cur >= m) cur -= m;
+        if (cur >= m) cur %= m;   // (m < V)
+      }
+      if (l0 < sl.p)
+        for (int l = l0; l < sl.P; l += sl.p) sum = sum + slice[k * 64 + l];
+    }
+    store(r, sum);
+  }
+}
 
 // Row sums, the elements of one block through the lanes of a wave.  A lane takes the 16-byte slots s = lane, lane + P, ... of the block; slot s holds the
 // elements V s - A ... V s - A + V - 1 (A = elements by which the block starts behind a 16-byte boundary, so every whole slot is one aligned access; the
@@ -463,9 +466,8 @@ algebra_row_sums(const int* __restrict__ row_p, const int* __restrict__ col_i, c
   const int64_t base = roff[row];
   double* __restrict__ mine = partials + (size_t)sub * n_out;
   const int b0 = row_p[row] + sub, b1 = row_p[row + 1];
-  const int g = V == 1 ? 1 : (m % V == 0 ? V : (m % 2 == 0 ? 2 : 1));   // gcd(V, m), V = 1, 2 or 4
-  const int p = m / g;
-  if (p > 64) {
+  const RowSlots sl = row_slots_of<V>(m);
+  if (sl.p > 64) {
     for (int r0 = 0; r0 < m; r0 += 64) {
       const int r = r0 + lane;
       double acc = 0.0;
@@ -479,41 +481,20 @@ algebra_row_sums(const int* __restrict__ row_p, const int* __restrict__ col_i, c
     }
     return;
   }
-  const int P = (64 / p) * p;
   double acc[K];
 #pragma unroll
   for (int k = 0; k < K; ++k) acc[k] = 0.0;
-  if (lane < P)
+  if (lane < sl.P)
     for (int b = b0; b < b1; b += S) {
       const int ne = m * cs[col_i[b]];
       const int64_t off = blk_p[b];
       const T* d = data + off;
       const int a = vec_ok ? (int)(off & (V - 1)) : 0;   // (wave-uniform)
-      if (V == 1 || a == 0) row_sum_slots<T, 0>(d, ne, lane, P, vec_ok, what, acc);
-      else if (a == 1) row_sum_slots<T, 1 % V>(d, ne, lane, P, vec_ok, what, acc);
-      else if (a == 2) row_sum_slots<T, 2 % V>(d, ne, lane, P, vec_ok, what, acc);
-      else row_sum_slots<T, 3 % V>(d, ne, lane, P, vec_ok, what, acc);
+      DBCSR_AMD_BY_SHIFT(row_sum_slots, a, d, ne, lane, sl.P, vec_ok, what, acc);
     }
-  double* slice = red[threadIdx.x >> 6];
-#pragma unroll
-  for (int k = 0; k < K; ++k) slice[k * 64 + lane] = acc[k];
-  wave_lds_handover();   // (the slice is this wave's alone)
-  for (int r = lane; r < m; r += 64) {
-    double sum = 0.0;
-    for (int k = 0; k < K; ++k) {
-      // the lanes l with (V l + k - (V - 1)) mod m == r: the first one below the period p (found without touching LDS), then every p-th
-      int cur = ((k - (V - 1)) % m + m) % m, l0 = 0;
-      while (l0 < p && cur != r) {
-        ++l0;
-        cur += V;
-        if (cur >= m) cur -= m;
-        if (cur >= m) cur %= m;   // (m < V)
-      }
-      if (l0 < p)
-        for (int l = l0; l < P; l += p) sum += slice[k * 64 + l];
-    }
+  row_handover<V>(acc, red[threadIdx.x >> 6], lane, m, sl, [&](int r, double sum) {
     if (base + r < n_out) mine[base + r] = sum;
-  }
+  });
 }
 
 // out[i] = the sum of the S partial vectors in the order 0 ... S - 1, for i below *total (the full length, on the device); zero behind it
@@ -546,41 +527,31 @@ __global__ void __launch_bounds__(256) algebra_col_list(const int* __restrict__ 
 // len <= kStageElems elements at d (element `off` of a 16-byte aligned area) -> f of them in lds[0 ... len), with aligned 16-byte loads where vec_ok
 template <typename T>
 __device__ __forceinline__ void stage_absval(const T* __restrict__ d, int64_t off, int len, int lane, int vec_ok, int what, double* lds) {
-  constexpr int V = Pack16<T>::V;
-  if (V > 1 && vec_ok) {
-    const int h = head_of<T>(off), head = h < len ? h : len, nv = (len - head) / V, done = head + nv * V;
-    if (lane < head) lds[lane] = absval_of(d[lane], what);
-    const Pack16<T>* dv = reinterpret_cast<const Pack16<T>*>(d + head);
-    for (int q = lane; q < nv; q += 64) {
-      const Pack16<T> x = dv[q];
-#pragma unroll
-      for (int u = 0; u < V; ++u) lds[head + q * V + u] = absval_of(x.v[u], what);
-    }
-    if (done + lane < len) lds[done + lane] = absval_of(d[done + lane], what);
-  } else {
-    for (int e = lane; e < len; e += 64) lds[e] = absval_of(d[e], what);
-  }
+  walk_block_values(d, off, len, lane, 64, vec_ok, [&](int e, T x) { lds[e] = absval_of(x, what); });
 }
 
 // the same loads, f summed per lane in a register (the lab build's ablation of the column sums without LDS)
 template <typename T>
 __device__ __forceinline__ double sum_absval(const T* __restrict__ d, int64_t off, int len, int lane, int vec_ok, int what) {
-  constexpr int V = Pack16<T>::V;
   double s = 0.0;
-  if (V > 1 && vec_ok) {
-    const int h = head_of<T>(off), head = h < len ? h : len, nv = (len - head) / V, done = head + nv * V;
-    if (lane < head) s += absval_of(d[lane], what);
-    const Pack16<T>* dv = reinterpret_cast<const Pack16<T>*>(d + head);
-    for (int q = lane; q < nv; q += 64) {
-      const Pack16<T> x = dv[q];
-#pragma unroll
-      for (int u = 0; u < V; ++u) s += absval_of(x.v[u], what);
-    }
-    if (done + lane < len) s += absval_of(d[done + lane], what);
-  } else {
-    for (int e = lane; e < len; e += 64) s += absval_of(d[e], what);
-  }
+  walk_block_values(d, off, len, lane, 64, vec_ok, [&](int, T x) { s += absval_of(x, what); });
   return s;
+}
+
+// What the column passes share (algebra_col_sums, algebra_matvec_cols): the staged piece holds the elements c0 ... c0 + len - 1 of the part, the lane's run
+// is run0 ... run0 + m - 1.  A lane that owns a column adds what the piece holds of its run, starting at element lane mod (that count) of it and wrapping
+template <typename Acc>
+__device__ __forceinline__ void add_run_rotated(const Acc* lds, int c0, int len, int run0, int m, int lane, bool owns, Acc& acc) {
+  const int lo = run0 > c0 ? run0 : c0, hi = run0 + m < c0 + len ? run0 + m : c0 + len;
+  if (owns && lo < hi) {
+    const int cnt = hi - lo;
+    const Acc* run = lds + (lo - c0);
+    int i = lane % cnt;
+    for (int k = 0; k < cnt; ++k) {
+      acc = acc + run[i];
+      if (++i == cnt) i = 0;
+    }
+  }
 }
 
 // sum_i f(a_ij) per full column: S waves per block column walk its list (wave sub takes the entries sub, sub + S, ...); a block is one contiguous piece of
@@ -635,16 +606,7 @@ algebra_col_sums(const int* __restrict__ col_p, const int* __restrict__ list, co
         if constexpr (VARIANT == 1) {
           if (lane < len) acc += lds[lane];
         } else {
-          const int lo = run0 > c0 ? run0 : c0, hi = run0 + m < c0 + len ? run0 + m : c0 + len;
-          if (lane < nj && lo < hi) {
-            const int cnt = hi - lo;
-            const double* run = lds + (lo - c0);
-            int i = lane % cnt;
-            for (int k = 0; k < cnt; ++k) {
-              acc += run[i];
-              if (++i == cnt) i = 0;
-            }
-          }
+          add_run_rotated(lds, c0, len, run0, m, lane, lane < nj, acc);
         }
         wave_lds_handover();   // (the next piece overwrites the slice)
       }
@@ -670,7 +632,6 @@ template <typename T>
 __global__ void __launch_bounds__(256) algebra_maxabs(const int* __restrict__ row_p, const int* __restrict__ col_i, const int64_t* __restrict__ blk_p,
                                                       const T* __restrict__ data, const int* __restrict__ rs, const int* __restrict__ cs, int nbr, int S,
                                                       int vec_ok, double* __restrict__ partials) {
-  constexpr int V = Pack16<T>::V;
   const int lane = threadIdx.x & 63;
   const int64_t wv = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int row = (int)(wv / S), sub = (int)(wv % S);
@@ -680,20 +641,7 @@ __global__ void __launch_bounds__(256) algebra_maxabs(const int* __restrict__ ro
   for (int b = row_p[row] + sub; b < row_p[row + 1]; b += S) {
     const int ne = m * cs[col_i[b]];
     const int64_t off = blk_p[b];
-    const T* d = data + off;
-    if (V > 1 && vec_ok) {
-      const int h = head_of<T>(off), head = h < ne ? h : ne, nv = (ne - head) / V, done = head + nv * V;
-      if (lane < head) acc = max_or_nan(acc, maxterm_of(d[lane]));
-      const Pack16<T>* dv = reinterpret_cast<const Pack16<T>*>(d + head);
-      for (int q = lane; q < nv; q += 64) {
-        const Pack16<T> x = dv[q];
-#pragma unroll
-        for (int u = 0; u < V; ++u) acc = max_or_nan(acc, maxterm_of(x.v[u]));
-      }
-      if (done + lane < ne) acc = max_or_nan(acc, maxterm_of(d[done + lane]));
-    } else {
-      for (int e = lane; e < ne; e += 64) acc = max_or_nan(acc, maxterm_of(d[e]));
-    }
+    walk_block_values(data + off, off, ne, lane, 64, vec_ok, [&](int, T x) { acc = max_or_nan(acc, maxterm_of(x)); });
   }
   acc = wave_max(acc);
   if (lane == 0) partials[wv] = acc;
@@ -777,26 +725,17 @@ algebra_scale_by_vector(const int* __restrict__ row_p, const int* __restrict__ c
       const int64_t idx = vb + (side ? e / m : e % m);
       if (idx < n) d[e] = d[e] * vec[idx];
     };
-    if (V == 1 || !vec_ok) {
-      for (int e = lane; e < ne; e += 64) one(e);
-      continue;
-    }
-    const int h = head_of<T>(off), head = h < ne ? h : ne, nv = (ne - head) / V, done = head + nv * V;
-    if (lane < head) one(lane);
-    Pack16<T>* dv = reinterpret_cast<Pack16<T>*>(d + head);
-    for (int q = lane; q < nv; q += 64) {
-      const int e = head + q * V;
+    walk_block<T>(off, ne, lane, 64, vec_ok, one, [&](int e) {
       int i = e % m, j = e / m;
-      Pack16<T> x = dv[q];
+      Pack16<T> x = *reinterpret_cast<Pack16<T>*>(d + e);
 #pragma unroll
       for (int u = 0; u < V; ++u) {
         const int64_t idx = vb + (side ? j : i);
         if (idx < n) x.v[u] = x.v[u] * vec[idx];
         if (++i == m) i = 0, ++j;
       }
-      dv[q] = x;
-    }
-    if (done + lane < ne) one(done + lane);
+      *reinterpret_cast<Pack16<T>*>(d + e) = x;
+    });
   }
 }
 
@@ -874,9 +813,8 @@ algebra_matvec_rows(const int* __restrict__ row_p, const int* __restrict__ col_i
   const int64_t base = yoff[row];
   Acc* __restrict__ mine = partials + (size_t)sub * n_y;
   const int b0 = row_p[row] + sub, b1 = row_p[row + 1];
-  const int g = V == 1 ? 1 : (m % V == 0 ? V : (m % 2 == 0 ? 2 : 1));   // gcd(V, m), V = 1, 2 or 4
-  const int p = m / g;
-  if (p > 64) {
+  const RowSlots sl = row_slots_of<V>(m);
+  if (sl.p > 64) {
     for (int r0 = 0; r0 < m; r0 += 64) {
       const int r = r0 + lane;
       Acc acc = Acc(0.0);
@@ -894,11 +832,10 @@ algebra_matvec_rows(const int* __restrict__ row_p, const int* __restrict__ col_i
     }
     return;
   }
-  const int P = (64 / p) * p;
   Acc acc[K];
 #pragma unroll
   for (int k = 0; k < K; ++k) acc[k] = Acc(0.0);
-  if (lane < P)
+  if (lane < sl.P)
     for (int b = b0; b < b1; b += S) {
       const int c = col_i[b];
       if (skip_diag && c == row) continue;   // (wave-uniform)
@@ -908,31 +845,11 @@ algebra_matvec_rows(const int* __restrict__ row_p, const int* __restrict__ col_i
       const T* xc = x + xb;
       const int64_t nx = n_x - xb;
       const int a = vec_ok ? (int)(off & (V - 1)) : 0;   // (wave-uniform)
-      if (V == 1 || a == 0) matvec_row_slots<T, 0>(d, ne, m, lane, P, vec_ok, conj, xc, nx, acc);
-      else if (a == 1) matvec_row_slots<T, 1 % V>(d, ne, m, lane, P, vec_ok, conj, xc, nx, acc);
-      else if (a == 2) matvec_row_slots<T, 2 % V>(d, ne, m, lane, P, vec_ok, conj, xc, nx, acc);
-      else matvec_row_slots<T, 3 % V>(d, ne, m, lane, P, vec_ok, conj, xc, nx, acc);
+      DBCSR_AMD_BY_SHIFT(matvec_row_slots, a, d, ne, m, lane, sl.P, vec_ok, conj, xc, nx, acc);
     }
-  Acc* slice = red[threadIdx.x >> 6];
-#pragma unroll
-  for (int k = 0; k < K; ++k) slice[k * 64 + lane] = acc[k];
-  wave_lds_handover();   // (the slice is this wave's alone)
-  for (int r = lane; r < m; r += 64) {
-    Acc sum = Acc(0.0);
-    for (int k = 0; k < K; ++k) {
-      // the lanes l with (V l + k - (V - 1)) mod m == r, as in algebra_row_sums
-      int cur = ((k - (V - 1)) % m + m) % m, l0 = 0;
-      while (l0 < p && cur != r) {
-        ++l0;
-        cur += V;
-        if (cur >= m) cur -= m;
-        if (cur >= m) cur %= m;   // (m < V)
-      }
-      if (l0 < p)
-        for (int l = l0; l < P; l += p) sum = sum + slice[k * 64 + l];
-    }
+  row_handover<V>(acc, red[threadIdx.x >> 6], lane, m, sl, [&](int r, Acc sum) {
     if (base + r < n_y) mine[base + r] = sum;
-  }
+  });
 }
 
 // elements of a staged piece: a workgroup's four slices stay within the 32 KB of kStageElems doubles per wave (a complex term is two doubles)
@@ -951,24 +868,15 @@ __device__ __forceinline__ void stage_matvec(const T* __restrict__ d, int64_t of
     const int i = (first + e) % m;
     lds[e] = i < nx ? matvec_term(d[e], xr[i], conj) : Acc(0.0);
   };
-  if (V > 1 && vec_ok) {
-    const int h = head_of<T>(off), head = h < len ? h : len, nv = (len - head) / V, done = head + nv * V;
-    if (lane < head) one(lane);
-    const Pack16<T>* dv = reinterpret_cast<const Pack16<T>*>(d + head);
-    for (int q = lane; q < nv; q += 64) {
-      const Pack16<T> a = dv[q];
-      const int e = head + q * V;
-      int i = (first + e) % m;
+  walk_block<T>(off, len, lane, 64, vec_ok, one, [&](int e) {
+    const Pack16<T> a = *reinterpret_cast<const Pack16<T>*>(d + e);
+    int i = (first + e) % m;
 #pragma unroll
-      for (int u = 0; u < V; ++u) {
-        lds[e + u] = i < nx ? matvec_term(a.v[u], xr[i], conj) : Acc(0.0);
-        if (++i == m) i = 0;
-      }
+    for (int u = 0; u < V; ++u) {
+      lds[e + u] = i < nx ? matvec_term(a.v[u], xr[i], conj) : Acc(0.0);
+      if (++i == m) i = 0;
     }
-    if (done + lane < len) one(done + lane);
-  } else {
-    for (int e = lane; e < len; e += 64) one(e);
-  }
+  });
 }
 
 // partials[sub * n_y + yoff[c] + j] = sum over the entries sub, sub + S, ... of block column c's list of sum_i g(a_ij) x[xoff[r] + i]: the staged form of
@@ -1005,16 +913,7 @@ algebra_matvec_cols(const int* __restrict__ col_p, const int* __restrict__ list,
         const int len = total - c0 < kPiece ? total - c0 : kPiece;
         stage_matvec(data + off + c0, off + c0, len, c0, m, lane, vec_ok, conj, x + xb, n_x - xb, lds);
         wave_lds_handover();   // (the slice is this wave's alone)
-        const int lo = run0 > c0 ? run0 : c0, hi = run0 + m < c0 + len ? run0 + m : c0 + len;
-        if (lane < nj && lo < hi) {
-          const int cnt = hi - lo;
-          const Acc* run = lds + (lo - c0);
-          int i = lane % cnt;
-          for (int k = 0; k < cnt; ++k) {
-            acc = acc + run[i];
-            if (++i == cnt) i = 0;
-          }
-        }
+        add_run_rotated(lds, c0, len, run0, m, lane, lane < nj, acc);
         wave_lds_handover();   // (the next piece overwrites the slice)
       }
     }
@@ -1063,6 +962,8 @@ algebra_matvec_combine(const typename MatvecAcc<T>::type* __restrict__ partials,
   if (!(mode & kMatvecBetaZero)) r = r + beta * matvec_wide(y[i]);
   y[i] = matvec_narrow<T>(r);
 }
+
+#undef DBCSR_AMD_BY_SHIFT
 
 }  // namespace dbcsr_amd
 #endif

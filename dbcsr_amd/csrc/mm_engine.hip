@@ -24,7 +24,8 @@
 //   mm_numeric_f64 / mm_numeric_f32                        blocks above 32 (32 x 32 tiles, fragments from global memory)
 //   mm_numeric_z64<MA,NC>                                  complex_8, any sizes: two accumulator sets, operands in slabs of 8 inner indices (mm_numeric_z64.h)
 // Around them: transpose, checksum, synthetic fill, norm filter, crop / window scale (submatrix limits), and the algebra between multiplies
-// (mm_algebra.h: add, add_on_diag, trace, dot, Frobenius norm).
+// (mm_algebra.h: add, add_on_diag, trace, dot, Frobenius norm, the norms and vectors, the matrix-vector product; mm_multivec.h; mm_rank_update.h; the walk
+// over the elements of a block that they share: mm_block_walk.h).
 //
 // Files of this translation unit (included below, inside namespace dbcsr_amd unless they open it themselves):
 //   mm_choose.h          WHICH kernel runs: SizeFacts / Switches / LabSwitches -> NumericChoice, the instance lists and their predicates (plain C++, no HIP)
@@ -35,7 +36,8 @@
 //   mm_engine_plan.h     plan reuse
 //   mm_engine_lab.h      lab build: hosts of the experimental dataflows and their family switch
 //   mm_engine_ops.h      init_c, crop, filter, checksum, fill, transpose, twin moves, statistics
-//   mm_engine_algebra.h  add (count / apply), add_on_diag pieces, trace, dot, norm (kernels: mm_algebra.h)
+//   mm_engine_algebra.h  add (count / apply), add_on_diag pieces, trace, dot, norm, norms and vectors, matvec, multivec, rank update (kernels: mm_algebra.h,
+//                        mm_multivec.h, mm_rank_update.h, over the block walk of mm_block_walk.h)
 // This file: create / destroy, the symbolic phase, and the numeric phase as a sequence -- product lists, choice, set-up, launch, plan bookkeeping.
 #include <hip/hip_runtime.h>
 
@@ -62,7 +64,7 @@
 #include "mm_numeric_f32.h"
 #include "mm_numeric_z64.h"   // complex_8: one family for every block size
 #include "mm_aux.h"
-#include "mm_algebra.h"   // add, add_on_diag, trace, dot, norm: the operations between multiplies
+#include "mm_algebra.h"   // add, add_on_diag, trace, dot, norm: the operations between multiplies (brings mm_block_walk.h: Pack16, walk_block)
 #include "mm_multivec.h"  // the matrix times several dense vectors
 #include "mm_rank_update.h"  // the rank-k update on the stored pattern
 // The library comes in two builds (Makefile): the SHIPPING one holds what a multiply can run by itself -- the kernels listed above, their

@@ -14,9 +14,32 @@ template <> inline float algebra_scalar<float>(const double s[2]) { return (floa
 template <> inline z64 algebra_scalar<z64>(const double s[2]) { return z64(s[0], s[1]); }
 
 static inline bool algebra_is_one(libsmm_acc_data_t datatype, const double s[2]) { return s[0] == 1.0 && (datatype != dbcsr_type_complex_8 || s[1] == 0.0); }
+static inline bool algebra_is_zero(libsmm_acc_data_t datatype, const double s[2]) { return s[0] == 0.0 && (datatype != dbcsr_type_complex_8 || s[1] == 0.0); }
 static inline int aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0 ? 1 : 0; }
 static inline bool algebra_type(libsmm_acc_data_t datatype) {
   return datatype == dbcsr_type_real_8 || datatype == dbcsr_type_real_4 || datatype == dbcsr_type_complex_8;
+}
+
+// F<element type>(...) for a `datatype` that algebra_type() accepted (an expression: it has F's value where F returns one).  The one place of this file
+// that turns a data type into an element type; dbcsr_amd_bcsr_dot, which offers two of the three, chooses for itself.
+#define DBCSR_AMD_BY_TYPE(F, ...)                                  \
+  (datatype == dbcsr_type_real_8   ? F<double>(__VA_ARGS__)        \
+   : datatype == dbcsr_type_real_4 ? F<float>(__VA_ARGS__)         \
+                                   : F<z64>(__VA_ARGS__))
+
+template <typename T> static inline size_t algebra_sizeof() { return sizeof(T); }
+static inline size_t algebra_esize(libsmm_acc_data_t datatype) { return DBCSR_AMD_BY_TYPE(algebra_sizeof); }
+
+// `mode` of the matvec family (matvec, multivec, rank update): *product = alpha != 0 and there is something to multiply (`operands`); without a product
+// the operands are not read and the result is beta times what was there
+static inline int product_mode(libsmm_acc_data_t datatype, const double alpha[2], const double beta[2], bool operands, bool* product) {
+  *product = !algebra_is_zero(datatype, alpha) && operands;
+  return (*product ? 0 : kMatvecNoProduct) | (algebra_is_zero(datatype, beta) ? kMatvecBetaZero : 0);
+}
+
+// the `trans` and `kind` arguments of matvec and multivec: an operation N, T or C; no symmetry (-1) or the stored triangle of a square matrix (0 ... 3)
+static inline bool matvec_args_ok(char trans, int kind, const dbcsr_amd_bcsr* a) {
+  return (trans == 'N' || trans == 'T' || trans == 'C') && kind >= -1 && kind <= 3 && (kind < 0 || a->nblkrows == a->nblkcols);
 }
 
 // waves per block row of the per-block add: about four result blocks per wave (config 2's shape at 50 % overlap: 3.35 ms, against 3.52 ms with row_split's
@@ -193,12 +216,7 @@ int dbcsr_amd_bcsr_add_apply(void* handle, libsmm_acc_data_t datatype, const dou
     if (E->add_nblks == 0) return 0;
     if (dst->col_i != a->col_i) ACC_CHECK(hipMemcpyAsync(dst->col_i, a->col_i, sizeof(int32_t) * (size_t)a->nblks, hipMemcpyDeviceToDevice, st));
     if (dst->blk_p != a->blk_p) ACC_CHECK(hipMemcpyAsync(dst->blk_p, a->blk_p, sizeof(int64_t) * (size_t)a->nblks, hipMemcpyDeviceToDevice, st));
-    if (datatype == dbcsr_type_real_8)
-      add_flat_launch<double>(st, a, b, dst, E->add_nze, alpha, beta, mode);
-    else if (datatype == dbcsr_type_real_4)
-      add_flat_launch<float>(st, a, b, dst, E->add_nze, alpha, beta, mode);
-    else
-      add_flat_launch<z64>(st, a, b, dst, E->add_nze, alpha, beta, mode);
+    DBCSR_AMD_BY_TYPE(add_flat_launch, st, a, b, dst, E->add_nze, alpha, beta, mode);
     return check(hipGetLastError(), "dbcsr_amd_bcsr_add_apply", __FILE__, __LINE__);
   }
   plan_invalidate(E);  // this call uses the engine's work areas: the next multiply runs its own symbolic phase
@@ -209,12 +227,7 @@ int dbcsr_amd_bcsr_add_apply(void* handle, libsmm_acc_data_t datatype, const dou
   hipLaunchKernelGGL(algebra_emit, grid_for((int64_t)nbr * W), dim3(256), 0, st, a->row_p, a->blk_p, E->cin_bm.p, E->cin_pre.p, b->row_p, b->blk_p,
                      E->add_beta_zero ? (const uint32_t*)nullptr : E->b_bm.p, E->b_pre.p, E->c_bm.p, E->c_pre.p, dst->row_p, E->c_blk_p_ws.p, nbr, W,
                      dst->col_i, dst->blk_p, E->prod_start.p);
-  if (datatype == dbcsr_type_real_8)
-    add_blocks_launch<double>(E, st, a, b, dst, alpha, beta, mode);
-  else if (datatype == dbcsr_type_real_4)
-    add_blocks_launch<float>(E, st, a, b, dst, alpha, beta, mode);
-  else
-    add_blocks_launch<z64>(E, st, a, b, dst, alpha, beta, mode);
+  DBCSR_AMD_BY_TYPE(add_blocks_launch, E, st, a, b, dst, alpha, beta, mode);
   return check(hipGetLastError(), "dbcsr_amd_bcsr_add_apply", __FILE__, __LINE__);
 }
 
@@ -249,12 +262,7 @@ static int diag_any(void* handle, libsmm_acc_data_t datatype, bool fill, const d
   if (!algebra_type(datatype)) return -10;
   hipStream_t st = stream_of(stream);
   if (m->nblkrows == 0 || m->nblks == 0) return 0;
-  if (datatype == dbcsr_type_real_8)
-    diag_launch<double>(st, fill, m, alpha);
-  else if (datatype == dbcsr_type_real_4)
-    diag_launch<float>(st, fill, m, alpha);
-  else
-    diag_launch<z64>(st, fill, m, alpha);
+  DBCSR_AMD_BY_TYPE(diag_launch, st, fill, m, alpha);
   return check(hipGetLastError(), fill ? "dbcsr_amd_bcsr_diag_fill" : "dbcsr_amd_bcsr_diag_shift", __FILE__, __LINE__);
 }
 
@@ -273,9 +281,7 @@ int dbcsr_amd_bcsr_trace(void* handle, libsmm_acc_data_t datatype, const dbcsr_a
   hipStream_t st = stream_of(stream);
   out[0] = out[1] = 0.0;
   if (m->nblkrows == 0 || m->nblks == 0) return 0;
-  const int64_t nw = datatype == dbcsr_type_real_8   ? reduce_launch<double>(E, st, 0, m, 0)
-                     : datatype == dbcsr_type_real_4 ? reduce_launch<float>(E, st, 0, m, 0)
-                                                     : reduce_launch<z64>(E, st, 0, m, 0);
+  const int64_t nw = DBCSR_AMD_BY_TYPE(reduce_launch, E, st, 0, m, 0);
   return reduce_finish(E, st, nw, out, "dbcsr_amd_bcsr_trace");
 }
 
@@ -286,10 +292,7 @@ int dbcsr_amd_bcsr_norm2(void* handle, libsmm_acc_data_t datatype, const dbcsr_a
   hipStream_t st = stream_of(stream);
   out[0] = 0.0;
   if (m->nblkrows == 0 || m->nblks == 0) return 0;
-  const int sym = symmetric ? 1 : 0;
-  const int64_t nw = datatype == dbcsr_type_real_8   ? reduce_launch<double>(E, st, 1, m, sym)
-                     : datatype == dbcsr_type_real_4 ? reduce_launch<float>(E, st, 1, m, sym)
-                                                     : reduce_launch<z64>(E, st, 1, m, sym);
+  const int64_t nw = DBCSR_AMD_BY_TYPE(reduce_launch, E, st, 1, m, symmetric ? 1 : 0);
   double two[2] = {0.0, 0.0};
   const int rc = reduce_finish(E, st, nw, two, "dbcsr_amd_bcsr_norm2");
   out[0] = two[0];
@@ -408,13 +411,6 @@ static int scalar_finish(Engine* E, hipStream_t st, const double* dev, double ou
 }
 }  // extern "C++"
 
-#define DBCSR_AMD_BY_TYPE(F, ...)                                              \
-  do {                                                                         \
-    if (datatype == dbcsr_type_real_8) F<double>(__VA_ARGS__);                 \
-    else if (datatype == dbcsr_type_real_4) F<float>(__VA_ARGS__);             \
-    else F<z64>(__VA_ARGS__);                                                  \
-  } while (0)
-
 int dbcsr_amd_bcsr_maxabs(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, double out[1], void* stream) {
   Engine* E = static_cast<Engine*>(handle);
   if (!E || !m || !out) return -1;
@@ -507,9 +503,8 @@ static int diag_vector(void* handle, libsmm_acc_data_t datatype, bool set, const
   if (!algebra_type(datatype)) return -10;
   hipStream_t st = stream_of(stream);
   if (n == 0) return 0;
-  const size_t esize = datatype == dbcsr_type_real_8 ? 8 : datatype == dbcsr_type_real_4 ? 4 : 16;
   if (m->nblkrows == 0 || m->nblks == 0) {
-    if (!set) ACC_CHECK(hipMemsetAsync(vec, 0, esize * (size_t)n, st));
+    if (!set) ACC_CHECK(hipMemsetAsync(vec, 0, algebra_esize(datatype) * (size_t)n, st));
     return 0;
   }
   const int64_t *roff = nullptr, *coff = nullptr;
@@ -591,18 +586,16 @@ int dbcsr_amd_bcsr_matvec(void* handle, libsmm_acc_data_t datatype, char trans, 
                           int64_t n_x, const double beta[2], void* y, int64_t n_y, void* stream) {
   Engine* E = static_cast<Engine*>(handle);
   if (!E || !alpha || !a || !beta || n_x < 0 || n_y < 0 || (n_x > 0 && !x) || (n_y > 0 && !y)) return -1;
-  if (trans != 'N' && trans != 'T' && trans != 'C') return -1;
-  if (kind < -1 || kind > 3 || (kind >= 0 && a->nblkrows != a->nblkcols)) return -1;
+  if (!matvec_args_ok(trans, kind, a)) return -1;
   if (!algebra_type(datatype)) return -10;
-  const size_t esize = datatype == dbcsr_type_real_8 ? 8 : datatype == dbcsr_type_real_4 ? 4 : 16;
+  const size_t esize = algebra_esize(datatype);
   const uintptr_t x0 = reinterpret_cast<uintptr_t>(x), y0 = reinterpret_cast<uintptr_t>(y);
   if (n_x > 0 && n_y > 0 && x0 < y0 + esize * (size_t)n_y && y0 < x0 + esize * (size_t)n_x) return -1;   // x and y must not overlap
   hipStream_t st = stream_of(stream);
   if (n_y == 0 || a->nblkrows == 0 || a->nblkcols == 0) return 0;   // (no full row: nothing to write)
   const bool zc = datatype == dbcsr_type_complex_8;
-  const bool alpha_zero = alpha[0] == 0.0 && (!zc || alpha[1] == 0.0), beta_zero = beta[0] == 0.0 && (!zc || beta[1] == 0.0);
-  const bool product = !alpha_zero && a->nblks > 0;   // alpha == 0: A and x are not read; an empty matrix: y <- beta y
-  const int mode = (product ? 0 : kMatvecNoProduct) | (beta_zero ? kMatvecBetaZero : 0);
+  bool product = false;   // alpha == 0: A and x are not read; an empty matrix: y <- beta y
+  const int mode = product_mode(datatype, alpha, beta, a->nblks > 0, &product);
   MatvecPass rp = {0, 0, 0, 1.0}, cp = rp;
   if (product) matvec_passes(kind, trans, &rp, &cp);
   const int S_r = rp.on ? row_split(a->nblkrows, a->nblks) : 0, S_c = cp.on ? row_split(a->nblkcols, a->nblks) : 0;
@@ -655,10 +648,9 @@ int dbcsr_amd_bcsr_multivec(void* handle, libsmm_acc_data_t datatype, char trans
   Engine* E = static_cast<Engine*>(handle);
   if (!E || !alpha || !a || !beta || n_x < 0 || n_y < 0 || nrhs < 0 || ldx < nrhs || ldy < nrhs) return -1;
   if (nrhs > 0 && ((n_x > 0 && !x) || (n_y > 0 && !y))) return -1;
-  if (trans != 'N' && trans != 'T' && trans != 'C') return -1;
-  if (kind < -1 || kind > 3 || (kind >= 0 && a->nblkrows != a->nblkcols)) return -1;
+  if (!matvec_args_ok(trans, kind, a)) return -1;
   if (!algebra_type(datatype)) return -10;
-  const size_t esize = datatype == dbcsr_type_real_8 ? 8 : datatype == dbcsr_type_real_4 ? 4 : 16;
+  const size_t esize = algebra_esize(datatype);
   if (nrhs > 0 && n_x > 0 && n_y > 0) {   // the element ranges of X and Y must not overlap
     const uintptr_t x0 = reinterpret_cast<uintptr_t>(x), y0 = reinterpret_cast<uintptr_t>(y);
     const uintptr_t x1 = x0 + esize * ((size_t)(n_x - 1) * (size_t)ldx + (size_t)nrhs), y1 = y0 + esize * ((size_t)(n_y - 1) * (size_t)ldy + (size_t)nrhs);
@@ -667,9 +659,8 @@ int dbcsr_amd_bcsr_multivec(void* handle, libsmm_acc_data_t datatype, char trans
   hipStream_t st = stream_of(stream);
   if (nrhs == 0 || n_y == 0 || a->nblkrows == 0 || a->nblkcols == 0) return 0;   // (no element of Y below the full length: nothing to write)
   const bool zc = datatype == dbcsr_type_complex_8;
-  const bool alpha_zero = alpha[0] == 0.0 && (!zc || alpha[1] == 0.0), beta_zero = beta[0] == 0.0 && (!zc || beta[1] == 0.0);
-  const bool product = !alpha_zero && a->nblks > 0;   // alpha == 0: A and X are not read; an empty matrix: Y <- beta Y
-  const int mode = (product ? 0 : kMatvecNoProduct) | (beta_zero ? kMatvecBetaZero : 0);
+  bool product = false;   // alpha == 0: A and X are not read; an empty matrix: Y <- beta Y
+  const int mode = product_mode(datatype, alpha, beta, a->nblks > 0, &product);
   MatvecPass rp = {0, 0, 0, 1.0}, cp = rp;
   if (product) matvec_passes(kind, trans, &rp, &cp);
   const int ntiles = (nrhs + kMultivecTile - 1) / kMultivecTile, G = ntiles;   // (workgroups per block row and sub: at most one per tile)
@@ -713,18 +704,16 @@ int dbcsr_amd_bcsr_rank_update(void* handle, libsmm_acc_data_t datatype, char tr
   if (!E || !alpha || !a || !beta || n_x < 0 || n_y < 0 || nrhs < 0 || ldx < nrhs || ldy < nrhs) return -1;
   if (trans != 'T' && trans != 'C') return -1;
   if (!algebra_type(datatype)) return -10;
-  const bool zc = datatype == dbcsr_type_complex_8;
-  const bool alpha_zero = alpha[0] == 0.0 && (!zc || alpha[1] == 0.0), beta_zero = beta[0] == 0.0 && (!zc || beta[1] == 0.0);
-  const bool product = !alpha_zero && nrhs > 0;   // alpha == 0 or no column: X and Y are not read, A <- beta A
+  bool product = false;   // alpha == 0 or no column: X and Y are not read, A <- beta A
+  const int mode = product_mode(datatype, alpha, beta, nrhs > 0, &product);
   if (product && ((n_x > 0 && !x) || (n_y > 0 && !y))) return -1;
   hipStream_t st = stream_of(stream);
   if (a->nblkrows == 0 || a->nblkcols == 0 || a->nblks == 0) return 0;   // an empty matrix: nothing to write
   if (n_x == 0 || n_y == 0) return 0;                                      // (no element has both its rows)
   if (!product && algebra_is_one(datatype, beta)) return 0;               // A <- A: nothing is launched
-  const int mode = (product ? 0 : kMatvecNoProduct) | (beta_zero ? kMatvecBetaZero : 0);
   const int64_t *roff = nullptr, *coff = nullptr;
   if (vector_offsets(E, st, a, &roff, &coff)) return -1;
-  DBCSR_AMD_BY_TYPE(rank_update_launch, st, a, roff, coff, zc && trans == 'C' ? 1 : 0, alpha, beta, mode, nrhs, x, n_x, ldx, y, n_y, ldy);
+  DBCSR_AMD_BY_TYPE(rank_update_launch, st, a, roff, coff, datatype == dbcsr_type_complex_8 && trans == 'C' ? 1 : 0, alpha, beta, mode, nrhs, x, n_x, ldx, y, n_y, ldy);
   return check(hipGetLastError(), "dbcsr_amd_bcsr_rank_update", __FILE__, __LINE__);
 }
 #undef DBCSR_AMD_BY_TYPE

@@ -7,7 +7,8 @@
 // Dataflow: a workgroup of W <= 4 waves owns one block row (algebra_multivec_rows) or one block column (algebra_multivec_cols, over the per-column lists)
 // and W tiles of 16 right-hand sides, one tile per wave.  Lane 16 g + v holds column v of its tile and every fourth row (column pass: column) of the
 // block in 16 register accumulators: 64 rows at a time, a taller block row in chunks of 64.  A piece of the block -- whole element columns -- is loaded
-// by ALL waves of the workgroup (aligned 16-byte loads where the data area allows) into the workgroup's LDS, ONCE for its W tiles; each wave stages the
+// by ALL waves of the workgroup (walk_block of mm_block_walk.h over the workgroup's threads: aligned 16-byte loads where the data area allows) into the
+// workgroup's LDS, ONCE for its W tiles; each wave stages the
 // X rows of its own tile that the piece meets (one coalesced 16-entry read per row), and after a barrier multiplies: per element column j one LDS read
 // of x and one per owned row of a_ij.  W = 1 (nrhs <= 16) is the form with independent waves (measured against sharing: profiles/matrix_multivec.txt).  LDS is sized at the launch: W x 8 KB.
 // Partial results go to S_r + S_c compact n_y x nrhs matrices (one per wave of a block row / column, as the matvec's partial vectors);
@@ -30,21 +31,7 @@ static_assert(kMultivecABytes / 16 >= kMultivecRows, "a piece holds at least one
 // len elements at d (element `off` of a 16-byte aligned area) -> lds[0 ... len), by the nt threads of the workgroup: aligned 16-byte loads where vec_ok
 template <typename T>
 __device__ __forceinline__ void multivec_stage(const T* __restrict__ d, int64_t off, int len, int tid, int nt, int vec_ok, T* lds) {
-  constexpr int V = Pack16<T>::V;
-  if (V > 1 && vec_ok) {
-    const int h = head_of<T>(off), head = h < len ? h : len, nv = (len - head) / V, done = head + nv * V;
-    if (tid < head) lds[tid] = d[tid];
-    const Pack16<T>* dv = reinterpret_cast<const Pack16<T>*>(d + head);
-    for (int q = tid; q < nv; q += nt) {
-      const Pack16<T> a = dv[q];
-      const int e = head + q * V;
-#pragma unroll
-      for (int u = 0; u < V; ++u) lds[e + u] = a.v[u];
-    }
-    if (done + tid < len) lds[done + tid] = d[done + tid];
-  } else {
-    for (int e = tid; e < len; e += nt) lds[e] = d[e];
-  }
+  walk_block_values(d, off, len, tid, nt, vec_ok, [&](int e, T x) { lds[e] = x; });
 }
 
 // The column pass' piece, transposed on the way into the LDS so that the lanes of both passes read it alike: element (i, j) of an m x nj column-major
@@ -71,26 +58,17 @@ __device__ __forceinline__ void multivec_stage_transposed(const T* __restrict__ 
     else if (i >= m) i -= m, ++j;
     lds[i * nj + j] = d[e];
   };
-  if (V > 1 && vec_ok) {
-    const int hd = head_of<T>(off), head = hd < len ? hd : len, nv = (len - head) / V, done = head + nv * V;
-    if (tid < head) one(tid);
-    const Pack16<T>* dv = reinterpret_cast<const Pack16<T>*>(d + head);
-    for (int q = tid; q < nv; q += nt) {
-      const Pack16<T> a = dv[q];
-      const int e = head + q * V;
-      int j = (int)((float)e * rm), i = e - j * m;
-      if (i < 0) i += m, --j;
-      else if (i >= m) i -= m, ++j;
+  walk_block<T>(off, len, tid, nt, vec_ok, one, [&](int e) {
+    const Pack16<T> a = *reinterpret_cast<const Pack16<T>*>(d + e);
+    int j = (int)((float)e * rm), i = e - j * m;
+    if (i < 0) i += m, --j;
+    else if (i >= m) i -= m, ++j;
 #pragma unroll
-      for (int u = 0; u < V; ++u) {
-        lds[i * nj + j] = a.v[u];
-        if (++i == m) i = 0, ++j;
-      }
+    for (int u = 0; u < V; ++u) {
+      lds[i * nj + j] = a.v[u];
+      if (++i == m) i = 0, ++j;
     }
-    if (done + tid < len) one(done + tid);
-  } else {
-    for (int e = tid; e < len; e += nt) one(e);
-  }
+  });
 }
 
 // the X rows first ... first + nx - 1 of one tile -> xs[16 r + v] (zero for an entry at or behind row n_x or column nrhs: never read)

@@ -1,4 +1,4 @@
-"""The kernels of the matrix-vector product (dbcsr_amd/csrc/mm_algebra.h: algebra_matvec_rows, algebra_matvec_cols, algebra_matvec_combine), read from
+"""The kernels of the matrix-vector product (dbcsr_amd/csrc/mm_algebra.h over the block walk of mm_block_walk.h: algebra_matvec_rows, algebra_matvec_cols, algebra_matvec_combine), read from
 the code object of the shipping build (no GPU needed): each is there once per data type, uses no scratch and no more than 128 registers (four waves
 per SIMD), and the two passes keep their LDS -- the row pass' accumulators at the end of a block row, the column pass' staged piece of 1024 real or 512
 complex terms per wave -- within the 32 KB per workgroup that tests/test_kernel_resources_norms.py sets for the sums they are made from."""

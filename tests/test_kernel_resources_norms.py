@@ -1,4 +1,4 @@
-"""The kernels of the norms and vectors (dbcsr_amd/csrc/mm_algebra.h: row / column sums, max |x|, the diagonal as a vector, scale by vector), read from the
+"""The kernels of the norms and vectors (dbcsr_amd/csrc/mm_algebra.h over the block walk of mm_block_walk.h: row / column sums, max |x|, the diagonal as a vector, scale by vector), read from the
 code object of the shipping build (no GPU needed): every one is there under its name, for every data type it serves, and uses no scratch.  They stream
 memory: what matters is that none of them spills (the row sums keep 2 V - 1 accumulators per lane and choose among them by the block's alignment), and
 that none keeps so many registers that fewer than four waves fit a SIMD (<= 128)."""

@@ -1,4 +1,4 @@
-"""The kernels of the matrix algebra between multiplies (dbcsr_amd/csrc/mm_algebra.h: add, add_on_diag, trace, dot, Frobenius norm), read from the code
+"""The kernels of the matrix algebra between multiplies (dbcsr_amd/csrc/mm_algebra.h over the block walk of mm_block_walk.h: add, add_on_diag, trace, dot, Frobenius norm), read from the code
 object of the shipping build (no GPU needed): every one is there under its name, for every data type it serves, and uses no scratch.  They stream
 memory: what matters is that none of them spills, and that none keeps so many registers that fewer than four waves fit a SIMD (<= 128)."""
 import pytest
