@@ -160,6 +160,7 @@ int dbcsr_amd_bcsr_add_count(void* handle, const dbcsr_amd_bcsr* a, const dbcsr_
   // 2. the union pattern, in the symbolic phase's work areas
   plan_invalidate(E);
   E->valid = false;
+  engine_takes_work_areas(E);
   const int W = (nbc + 31) / 32;
   const size_t nw = (size_t)nbr * W;
   const int64_t cap = na + nb;   // (no more blocks than both operands have)
@@ -206,6 +207,7 @@ int dbcsr_amd_bcsr_add_apply(void* handle, libsmm_acc_data_t datatype, const dou
   if (!algebra_type(datatype)) return -10;
   const int pending = E->add_mode;
   E->add_mode = 0;
+  engine_writes_values(E);
   if (!pending || a->nblks != E->add_nblks_a || b->nblks != E->add_nblks_b || a->nblkrows != b->nblkrows || a->nblkcols != b->nblkcols ||
       dst->nblkrows != a->nblkrows || dst->nblkcols != a->nblkcols)
     return -1;
@@ -260,6 +262,7 @@ static int diag_any(void* handle, libsmm_acc_data_t datatype, bool fill, const d
   Engine* E = static_cast<Engine*>(handle);
   if (!E || !alpha || !m || m->nblkrows != m->nblkcols) return -1;
   if (!algebra_type(datatype)) return -10;
+  engine_writes_values(E);
   hipStream_t st = stream_of(stream);
   if (m->nblkrows == 0 || m->nblks == 0) return 0;
   DBCSR_AMD_BY_TYPE(diag_launch, st, fill, m, alpha);
@@ -501,6 +504,7 @@ static int diag_vector(void* handle, libsmm_acc_data_t datatype, bool set, const
   Engine* E = static_cast<Engine*>(handle);
   if (!E || !m || n < 0 || (n > 0 && !vec) || m->nblkrows != m->nblkcols) return -1;
   if (!algebra_type(datatype)) return -10;
+  if (set) engine_writes_values(E);
   hipStream_t st = stream_of(stream);
   if (n == 0) return 0;
   if (m->nblkrows == 0 || m->nblks == 0) {
@@ -525,6 +529,7 @@ int dbcsr_amd_bcsr_scale_by_vector(void* handle, libsmm_acc_data_t datatype, dbc
   Engine* E = static_cast<Engine*>(handle);
   if (!E || !m || n < 0 || (n > 0 && !vec) || (side != 0 && side != 1)) return -1;
   if (!algebra_type(datatype)) return -10;
+  engine_writes_values(E);
   hipStream_t st = stream_of(stream);
   if (n == 0 || m->nblkrows == 0 || m->nblks == 0) return 0;
   const int64_t *roff = nullptr, *coff = nullptr;
@@ -707,6 +712,7 @@ int dbcsr_amd_bcsr_rank_update(void* handle, libsmm_acc_data_t datatype, char tr
   bool product = false;   // alpha == 0 or no column: X and Y are not read, A <- beta A
   const int mode = product_mode(datatype, alpha, beta, nrhs > 0, &product);
   if (product && ((n_x > 0 && !x) || (n_y > 0 && !y))) return -1;
+  engine_writes_values(E);
   hipStream_t st = stream_of(stream);
   if (a->nblkrows == 0 || a->nblkcols == 0 || a->nblks == 0) return 0;   // an empty matrix: nothing to write
   if (n_x == 0 || n_y == 0) return 0;                                      // (no element has both its rows)

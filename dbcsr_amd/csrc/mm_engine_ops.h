@@ -16,6 +16,7 @@ static int init_c_any(void* handle, libsmm_acc_data_t datatype, double beta, dou
   hipStream_t st = stream_of(stream);
   const int nbr = E->facts.nbr, W = E->W;
   const int64_t nblk = E->facts.c_nblks;
+  engine_writes_values(E);
   c_out->nblks = nblk;
   if (nblk == 0) return 0;
   if (E->descs.ensure((size_t)nblk + 1)) return -1;
@@ -72,6 +73,7 @@ int dbcsr_amd_bcsr_crop_count(void* handle, libsmm_acc_data_t datatype, const db
   const int nbr = m->nblkrows;
   const int64_t nb = m->nblks;
   E->valid = false;  // shares workspace with the symbolic phase
+  engine_takes_work_areas(E);
   E->flt_nblks = nb;
   E->flt_new_nblks = -1;  // (keep / prod_start now describe the window, not a filter)
   E->crop_win = make_window(m, row_lo, row_hi, col_lo, col_hi);
@@ -103,6 +105,7 @@ int dbcsr_amd_bcsr_crop_apply(void* handle, libsmm_acc_data_t datatype, const db
   if (E) plan_invalidate(E);  // this call uses (or changes what feeds) the engine's work areas: the next multiply runs its own symbolic phase
   if (!E || !src || !dst || !E->crop_pending || E->flt_nblks != src->nblks) return -1;
   E->crop_pending = false;
+  engine_writes_values(E);
   hipStream_t st = stream_of(stream);
   const int nbr = src->nblkrows;
   if (nbr == 0 || src->nblks == 0) return 0;
@@ -127,6 +130,8 @@ static int scale_window_any(void* handle, libsmm_acc_data_t datatype, dbcsr_amd_
                             int64_t col_lo, int64_t col_hi, void* stream) {
   Engine* E = static_cast<Engine*>(handle);
   if (!E || !m) return -1;
+  engine_writes_values(E);
+  E->crop_pending = false;   // (off_a / off_b are rewritten below: a crop count that waits for its apply half is over)
   hipStream_t st = stream_of(stream);
   const int nbr = m->nblkrows;
   if (nbr == 0 || m->nblks == 0) return 0;
@@ -168,6 +173,7 @@ int dbcsr_amd_bcsr_filter_count(void* handle, libsmm_acc_data_t datatype, const 
   const int nbr = m->nblkrows;
   const int64_t nb = m->nblks;
   E->valid = false;  // shares workspace with the symbolic phase
+  engine_takes_work_areas(E);
   E->flt_nblks = nb;
   E->flt_new_nblks = -1;
   if (E->norms64.ensure((size_t)nb + 1) || E->keep.ensure((size_t)nb + 1) || E->blk_nze.ensure((size_t)nb + 1) ||
@@ -180,6 +186,7 @@ int dbcsr_amd_bcsr_filter_count(void* handle, libsmm_acc_data_t datatype, const 
   if (have_norms && E->unwritten_below > eps * eps) {
     fprintf(stderr, "dbcsr_amd_bcsr_filter_count: this matrix was multiplied with a final filter of eps^2 = %g announced (dbcsr_amd_mm_expect_filter); "
                     "blocks below that were not written and cannot be kept with eps^2 = %g\n", E->unwritten_below, eps * eps);
+    E->flt_nblks = -1;   // (nothing was counted: neither apply half may run)
     return -3;
   }
   E->norms_data = nullptr;
@@ -215,6 +222,7 @@ int dbcsr_amd_bcsr_filter_apply(void* handle, libsmm_acc_data_t datatype, const 
   Engine* E = static_cast<Engine*>(handle);
   if (E) plan_invalidate(E);  // this call uses (or changes what feeds) the engine's work areas: the next multiply runs its own symbolic phase
   if (!E || !src || !dst || E->flt_nblks != src->nblks) return -1;
+  engine_writes_values(E);
   hipStream_t st = stream_of(stream);
   const int nbr = src->nblkrows;
   if (nbr == 0 || src->nblks == 0) return 0;
@@ -263,6 +271,7 @@ int dbcsr_amd_bcsr_checksum(void* handle, libsmm_acc_data_t datatype, const dbcs
   const int nbr = m->nblkrows;
   out2[0] = out2[1] = 0.0;
   if (nbr == 0 || m->nblks == 0) return 0;
+  E->crop_pending = false;   // (off_a / off_b are rewritten below: a crop count that waits for its apply half is over)
   if (E->row_sums.ensure((size_t)2 * nbr + 2)) return -1;
   if (element_offsets(E, m->row_blk_size, nbr, E->off_a, st)) return -1;
   if (element_offsets(E, m->col_blk_size, m->nblkcols, E->off_b, st)) return -1;
@@ -290,6 +299,7 @@ int dbcsr_amd_bcsr_fill_random(void* handle, libsmm_acc_data_t datatype, const d
 int dbcsr_amd_bcsr_fill_random_dist(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, int counter,
                                     const int32_t* row_gid, const int32_t* col_gid, int32_t nblkrows_global, void* stream) {
   if (!handle || !m) return -1;
+  engine_writes_values(static_cast<Engine*>(handle));
   hipStream_t st = stream_of(stream);
   if (m->nblks == 0) return 0;
   if (datatype == dbcsr_type_real_8)
@@ -318,6 +328,8 @@ static int transpose_any(void* handle, libsmm_acc_data_t datatype, bool conj, co
   const int s_nbr = src->nblkrows, t_nbr = src->nblkcols;
   const int Wt = (s_nbr + 31) / 32;
   E->valid = false;  // shares workspace with the symbolic phase
+  engine_takes_work_areas(E);
+  engine_writes_values(E);
   if (E->c_bm.ensure((size_t)t_nbr * Wt + 1) || E->c_pre.ensure((size_t)t_nbr * Wt + 1) || E->row_nnz.ensure((size_t)t_nbr + 1) ||
       E->blk_nze.ensure((size_t)src->nblks + 1) || E->c_blk_p_ws.ensure((size_t)src->nblks + 1))
     return -1;
@@ -383,6 +395,7 @@ int dbcsr_amd_bcsr_twin_count(void* handle, const dbcsr_amd_bcsr* src, int mode,
   hipStream_t st = stream_of(stream);
   const int nbr = src->nblkrows, W = (nbr + 31) / 32;
   E->valid = false;  // shares workspace with the symbolic phase
+  engine_takes_work_areas(E);
   *nblks = *nze = 0;
   if (nbr == 0) return 0;
   if (E->c_bm.ensure((size_t)nbr * W + 1) || E->c_pre.ensure((size_t)nbr * W + 1) || E->row_nnz.ensure((size_t)nbr + 1) ||
@@ -415,6 +428,7 @@ int dbcsr_amd_bcsr_twin_apply(void* handle, libsmm_acc_data_t datatype, const db
   if (datatype != dbcsr_type_real_8 && datatype != dbcsr_type_real_4 && datatype != dbcsr_type_complex_8) return -10;
   hipStream_t st = stream_of(stream);
   const int nbr = src->nblkrows, W = (nbr + 31) / 32;
+  engine_writes_values(E);
   if (nbr == 0 || src->nblks == 0) return 0;
   if (datatype == dbcsr_type_real_8)
     hipLaunchKernelGGL((desym_fill<double>), grid_for((int64_t)nbr * 64), dim3(256), 0, st, src->row_p, src->col_i, src->blk_p,

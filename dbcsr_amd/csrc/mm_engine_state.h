@@ -179,6 +179,21 @@ struct Engine {
 #endif
 };
 
+// Every entry that writes a matrix's values passes through here before it launches: the block norms a numeric kernel left (norms_data, norms64) are those
+// of the values before the write, so dbcsr_amd_bcsr_filter_count must form them again.  (The engine does not know which matrix is written through a view
+// or another descriptor of the same data area: any write forgets them.)
+static inline void engine_writes_values(Engine* E) { E->norms_data = nullptr; }
+
+// The count halves of the two-call protocols (filter, crop, union add) leave their answer in work areas that the symbolic phase, each other's count, the
+// transpose and the twin moves write too.  Whoever is about to write those areas calls this first: a count that is still pending is over, and its apply
+// half then refuses (-1) and writes nothing instead of compacting by what this call left there.
+static inline void engine_takes_work_areas(Engine* E) {
+  E->flt_nblks = -1;
+  E->flt_new_nblks = -1;
+  E->crop_pending = false;
+  if (E->add_mode == 2) E->add_mode = 0;
+}
+
 KPassMemo* engine_kpass_memo(void* handle) { return handle ? &static_cast<Engine*>(handle)->kpass_memo : nullptr; }
 int engine_filter_in_place(void* handle) { return handle ? static_cast<Engine*>(handle)->filter_in_place : 0; }
 

@@ -94,7 +94,17 @@ int dbcsr_amd_mm_symbolic_filtered(void* handle, libsmm_acc_data_t datatype, dou
 /* Final block filter of a multiply (dbcsr_mm_multrec.F:694-748) / dbcsr_filter: blocks with sum x^2 < eps^2 are
  * dropped.  _count writes new_row_p [nblkrows+1] (device) and the new block/element counts (host, synchronises);
  * _apply then compacts index and data into caller-allocated dst arrays (dst->row_p = new_row_p).
- * complex_8: sum x^2 is sum re^2 + im^2. */
+ * complex_8: sum x^2 is sum re^2 + im^2.
+ * The two halves belong together (so do those of the crop and of the union add below): the count leaves its answer in work areas that the
+ * symbolic phase of a multiply, every other _count, the transpose and the twin moves use too.  Any of those between a _count and its _apply ends the
+ * pending count -- the _apply then returns -1 and writes nothing; count again.  (A reduction, a norm, a vector operation or a flat add in between is
+ * harmless: the algebra has buffers of its own.  A crop count is also ended by dbcsr_amd_bcsr_scale_window and dbcsr_amd_bcsr_checksum.)
+ * Block norms left by a multiply: the exact-size, slab and class kernels of a FILTERED fp64 multiply (dbcsr_amd_mm_symbolic_filtered with filter_eps > 0)
+ * leave every C block's squared norm behind, and a _filter_count on that C -- same data pointer, same block count -- uses them instead of a pass over C.
+ * The engine forgets them in the next symbolic phase, numeric phase or filter count, and in every entry that writes a matrix's values (init_c, scale_window,
+ * add_apply, the diagonal entries, set_diag, scale_by_vector, rank_update, fill_random, crop / filter apply, transpose, twin moves).  It cannot see a write
+ * made outside it: the norms are good only while nobody else writes C -- or frees it and allocates another matrix there -- between the numeric phase and
+ * the filter. */
 int dbcsr_amd_bcsr_filter_count(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, double eps, int32_t* new_row_p,
   int64_t* new_nblks, int64_t* new_nze, void* stream);
 int dbcsr_amd_bcsr_filter_apply(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, dbcsr_amd_bcsr* dst, void* stream);
@@ -288,7 +298,8 @@ int dbcsr_amd_mm_trust_plan(void* handle, int on);
 /* A filtered multiply (reference: src/mm/dbcsr_mm_multrec.F:373-383 -- the product of a multiply with filter_eps is filtered with the same eps before it is
    finalized): announce the final block filter of the NEXT dbcsr_amd_mm_numeric of this handle.  Its product kernels form a block's squared norm before they write it
    and leave a block with ||blk||^2 < eps^2 UNWRITTEN -- the block filter is going to drop it (same double, same comparison), nobody may read it before.  The C that
-   comes back is therefore only good for dbcsr_amd_bcsr_filter_count / _apply with an eps that is not smaller (a smaller one is refused: -3).  Ignored by
+   comes back is therefore only good for dbcsr_amd_bcsr_filter_count / _apply with an eps that is not smaller (a smaller one is refused: -3, nothing is counted), and
+   that filter comes before any other call that writes C.  Ignored by
    complex_8 multiplies (every block is written).  On products with many
    dropped blocks the dropped share of C's write traffic is saved.  Without this call every block is written.  Call it AFTER the symbolic phase of the
    multiply it is meant for (a symbolic phase cancels an announcement that was never consumed).  fp64; ignored for retain_sparsity and in-place accumulation. */
