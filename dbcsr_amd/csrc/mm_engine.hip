@@ -67,6 +67,7 @@
 #include "mm_algebra.h"   // add, add_on_diag, trace, dot, norm: the operations between multiplies (brings mm_block_walk.h: Pack16, walk_block)
 #include "mm_multivec.h"  // the matrix times several dense vectors
 #include "mm_rank_update.h"  // the rank-k update on the stored pattern
+#include "mm_block_inverse.h"  // the block diagonal: its copy and the batched inverse of its blocks
 // The library comes in two builds (Makefile): the SHIPPING one holds what a multiply can run by itself -- the kernels listed above, their
 // symbolic phases, plan reuse -- and the LAB one (-DDBCSR_AMD_EXPERIMENTS, libdbcsr_acc_amd_lab.so) adds every dataflow and variant that
 // was built, made parity-green and measured but does not win: the LDS-DMA ring kernels (mm_dma.h), XCD-wide C tiles (mm_tile.*), CU-wide

@@ -1,7 +1,7 @@
 // mm_engine_algebra.h -- part of mm_engine.hip (included inside extern "C", after mm_engine_ops.h): the C-ABI operations between multiplies --
 // dbcsr_amd_bcsr_add_count / _add_apply, the pieces of dbcsr_add_on_diag (dbcsr_amd_bcsr_diag_count / _diag_fill / _diag_shift), dbcsr_amd_bcsr_trace,
-// _dot, _norm2, and the norms and vectors: dbcsr_amd_bcsr_maxabs, _row_sums, _col_sums, _gershgorin, _get_diag, _set_diag, _scale_by_vector, _matvec, _multivec, _rank_update.
-// Kernels: mm_algebra.h, mm_multivec.h, mm_rank_update.h. The reductions, the diagonal pieces, the same-pattern add and the norms and vectors use buffers of their own (Engine::alg_*) and the
+// _dot, _norm2, and the norms and vectors: dbcsr_amd_bcsr_maxabs, _row_sums, _col_sums, _gershgorin, _get_diag, _set_diag, _scale_by_vector, _matvec, _multivec, _rank_update,
+// and the block diagonal: dbcsr_amd_bcsr_block_diag_count / _apply / _invert.  Kernels: mm_algebra.h, mm_multivec.h, mm_rank_update.h, mm_block_inverse.h. The reductions, the diagonal pieces, the same-pattern add and the norms and vectors use buffers of their own (Engine::alg_*) and the
 // scan's scratch, which no saved plan depends on (the checksum uses it the same way): they do NOT invalidate the plan.  The union add borrows the
 // symbolic phase's bitmaps and prefix arrays and invalidates it, as filter and crop do.
 #ifndef DBCSR_AMD_MM_ENGINE_ALGEBRA_H
@@ -721,6 +721,109 @@ int dbcsr_amd_bcsr_rank_update(void* handle, libsmm_acc_data_t datatype, char tr
   if (vector_offsets(E, st, a, &roff, &coff)) return -1;
   DBCSR_AMD_BY_TYPE(rank_update_launch, st, a, roff, coff, datatype == dbcsr_type_complex_8 && trans == 'C' ? 1 : 0, alpha, beta, mode, nrhs, x, n_x, ldx, y, n_y, ldy);
   return check(hipGetLastError(), "dbcsr_amd_bcsr_rank_update", __FILE__, __LINE__);
+}
+// ---- block diagonal (kernels: mm_block_inverse.h) ---------------------------------------------------------------------------------------------------------
+extern "C++" {
+template <typename T>
+static void block_diag_copy_launch(hipStream_t st, const dbcsr_amd_bcsr* src, dbcsr_amd_bcsr* dst) {
+  hipLaunchKernelGGL((block_diag_copy<T>), grid_for((int64_t)src->nblkrows * 64), dim3(256), 0, st, src->row_p, src->col_i, src->blk_p,
+                     static_cast<const T*>(src->data), dst->row_p, dst->col_i, dst->blk_p, static_cast<T*>(dst->data), src->row_blk_size, src->col_blk_size,
+                     src->nblkrows, aligned16(dst->data));
+}
+
+// more than 64 KB of dynamic LDS needs the attribute, once per kernel
+template <typename K>
+static int block_inverse_allow_lds(K kernel, size_t bytes, bool* done) {
+  if (*done || bytes <= 65536) return 0;
+  ACC_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  *done = true;
+  return 0;
+}
+
+// the wave kernel over every block row (it also counts the skipped blocks), and the workgroup kernel when a block above 32 may be there
+template <typename T>
+static int block_inverse_launch(hipStream_t st, dbcsr_amd_bcsr* m, int max_dim, unsigned long long* info) {
+  using Acc = typename MatvecAcc<T>::type;
+  static bool wave_lds = false, wide_lds = false;
+  const int nbr = m->nblkrows, vec_ok = aligned16(m->data);
+  const int nmax = std::max(1, std::min(max_dim, kBlockInverseWaveDim));
+  if (block_inverse_allow_lds(block_inverse_wave<T>, 4 * block_inverse_lds_bytes<Acc>(kBlockInverseWaveDim), &wave_lds)) return -1;
+  hipLaunchKernelGGL((block_inverse_wave<T>), grid_for((int64_t)nbr * 64), dim3(256), 4 * block_inverse_lds_bytes<Acc>(nmax), st, m->row_p, m->col_i,
+                     m->blk_p, static_cast<T*>(m->data), m->row_blk_size, m->col_blk_size, nbr, nmax, max_dim, vec_ok, info);
+  if (max_dim > kBlockInverseWaveDim) {
+    if (block_inverse_allow_lds(block_inverse_wide<T>, block_inverse_lds_bytes<Acc>(kBlockInverseMaxDim), &wide_lds)) return -1;
+    hipLaunchKernelGGL((block_inverse_wide<T>), dim3((unsigned)nbr), dim3(256), block_inverse_lds_bytes<Acc>(max_dim), st, m->row_p, m->col_i, m->blk_p,
+                       static_cast<T*>(m->data), m->row_blk_size, m->col_blk_size, nbr, max_dim, vec_ok, info);
+  }
+  return 0;
+}
+}  // extern "C++"
+
+int dbcsr_amd_bcsr_block_diag_count(void* handle, const dbcsr_amd_bcsr* m, int32_t* dst_row_p, int32_t* dst_col_i, int64_t* dst_blk_p, int64_t* nblks,
+                                    int64_t* nze, int32_t* max_dim, void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E || !m || !dst_row_p || !nblks || !nze || !max_dim || m->nblkrows != m->nblkcols) return -1;
+  hipStream_t st = stream_of(stream);
+  const int nbr = m->nblkrows;
+  *nblks = *nze = 0;
+  *max_dim = 0;
+  if (nbr > 0 && (!dst_col_i || !dst_blk_p)) return -1;
+  if (E->alg_i32.ensure(4 + 2 * (size_t)nbr) || E->alg_i64.ensure(8 + (size_t)nbr + 1)) return -1;
+  int* have = E->alg_i32.p + 4;
+  int* sizes = have + nbr;
+  int64_t* off = E->alg_i64.p + 8;
+  ACC_CHECK(hipMemsetAsync(E->alg_i64.p, 0, 2 * sizeof(int64_t), st));
+  ACC_CHECK(hipMemsetAsync(E->alg_i32.p, 0, sizeof(int), st));
+  if (nbr > 0)
+    hipLaunchKernelGGL(block_diag_find, grid_for((int64_t)nbr * 64), dim3(256), 0, st, m->row_p, m->col_i, m->row_blk_size, m->col_blk_size, nbr, have, sizes,
+                       E->alg_i32.p);
+  if (exclusive_scan<int32_t>(E, have, nbr, dst_row_p, E->alg_i64.p + 0, true, st)) return -1;
+  if (exclusive_scan<int64_t>(E, sizes, nbr, off, E->alg_i64.p + 1, false, st)) return -1;
+  if (nbr > 0) hipLaunchKernelGGL(diag_emit, grid_for(nbr), dim3(256), 0, st, have, dst_row_p, off, nbr, dst_col_i, dst_blk_p);
+  ACC_CHECK(hipMemcpyAsync(E->host_scalars, E->alg_i64.p, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  ACC_CHECK(hipMemcpyAsync(E->host_scalars + 2, E->alg_i32.p, sizeof(int), hipMemcpyDeviceToHost, st));
+  ACC_CHECK(hipStreamSynchronize(st));
+  *nblks = E->host_scalars[0];
+  *nze = E->host_scalars[1];
+  *max_dim = *reinterpret_cast<const int*>(E->host_scalars + 2);
+  return check(hipGetLastError(), "dbcsr_amd_bcsr_block_diag_count", __FILE__, __LINE__);
+}
+
+int dbcsr_amd_bcsr_block_diag_apply(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, dbcsr_amd_bcsr* dst, void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E || !src || !dst || src->nblkrows != src->nblkcols || dst->nblkrows != src->nblkrows || dst->nblkcols != src->nblkcols) return -1;
+  if (!algebra_type(datatype)) return -10;
+  if (dst->nblks > 0 && dst->data == src->data) return -1;   // (a copy between two data areas)
+  engine_writes_values(E);
+  hipStream_t st = stream_of(stream);
+  if (src->nblkrows == 0 || src->nblks == 0 || dst->nblks == 0) return 0;
+  DBCSR_AMD_BY_TYPE(block_diag_copy_launch, st, src, dst);
+  return check(hipGetLastError(), "dbcsr_amd_bcsr_block_diag_apply", __FILE__, __LINE__);
+}
+
+int dbcsr_amd_bcsr_block_diag_invert(void* handle, libsmm_acc_data_t datatype, dbcsr_amd_bcsr* m, int max_dim, int64_t info[3], void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E || !m || m->nblkrows != m->nblkcols || max_dim < 0) return -1;
+  if (!algebra_type(datatype)) return -10;
+  if (max_dim > kBlockInverseMaxDim) return -11;
+  if (info) info[0] = 0, info[1] = -1, info[2] = 0;
+  engine_writes_values(E);
+  hipStream_t st = stream_of(stream);
+  if (m->nblkrows == 0 || m->nblks == 0) return 0;
+  if (E->alg_i64.ensure(8)) return -1;
+  // [0] singular blocks, [1] the first of their block rows (all ones: none yet), [2] skipped blocks
+  unsigned long long* dev = reinterpret_cast<unsigned long long*>(E->alg_i64.p);
+  ACC_CHECK(hipMemsetAsync(dev, 0, 3 * sizeof(int64_t), st));
+  ACC_CHECK(hipMemsetAsync(dev + 1, 0xff, sizeof(int64_t), st));
+  if (DBCSR_AMD_BY_TYPE(block_inverse_launch, st, m, max_dim, dev)) return -1;
+  if (info) {
+    ACC_CHECK(hipMemcpyAsync(E->host_scalars, dev, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    ACC_CHECK(hipStreamSynchronize(st));
+    info[0] = E->host_scalars[0];
+    info[1] = E->host_scalars[0] > 0 ? E->host_scalars[1] : -1;
+    info[2] = E->host_scalars[2];
+  }
+  return check(hipGetLastError(), "dbcsr_amd_bcsr_block_diag_invert", __FILE__, __LINE__);
 }
 #undef DBCSR_AMD_BY_TYPE
 

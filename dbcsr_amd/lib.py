@@ -46,6 +46,8 @@ MM_SYMBOLS = [
     "dbcsr_amd_bcsr_maxabs", "dbcsr_amd_bcsr_row_sums", "dbcsr_amd_bcsr_col_sums", "dbcsr_amd_bcsr_gershgorin", "dbcsr_amd_bcsr_get_diag",
     "dbcsr_amd_bcsr_set_diag", "dbcsr_amd_bcsr_scale_by_vector", "dbcsr_amd_bcsr_matvec", "dbcsr_amd_bcsr_multivec",
     "dbcsr_amd_bcsr_rank_update",
+    # block diagonal
+    "dbcsr_amd_bcsr_block_diag_count", "dbcsr_amd_bcsr_block_diag_apply", "dbcsr_amd_bcsr_block_diag_invert",
 ]
 
 # `kind` of a matrix with symmetry in the C ABI (include/dbcsr_amd_mm.h): bit 0 negates the twin block, bit 1 conjugates it
@@ -209,6 +211,9 @@ def load_library(lab=False):
     L.dbcsr_amd_bcsr_matvec.argtypes = [vp, i32, C.c_char, Z, BP, i32, vp, i64, Z, vp, i64, vp]
     L.dbcsr_amd_bcsr_multivec.argtypes = [vp, i32, C.c_char, Z, BP, i32, i32, vp, i64, i64, Z, vp, i64, i64, vp]
     L.dbcsr_amd_bcsr_rank_update.argtypes = [vp, i32, C.c_char, Z, i32, vp, i64, i64, vp, i64, i64, Z, BP, vp]
+    L.dbcsr_amd_bcsr_block_diag_count.argtypes = [vp, BP, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32), vp]
+    L.dbcsr_amd_bcsr_block_diag_apply.argtypes = [vp, i32, BP, BP, vp]
+    L.dbcsr_amd_bcsr_block_diag_invert.argtypes = [vp, i32, BP, i32, C.POINTER(i64), vp]
     if lab:   # diagnostics of the experimental dataflows (dbcsr_amd/csrc/mm_lab_api.h): the shipping build does not export them
         L.dbcsr_amd_mm_tile_stats.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
         L.dbcsr_amd_mm_band_stats.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]

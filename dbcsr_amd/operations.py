@@ -15,6 +15,8 @@
     dbcsr_matvec(matrix, vec_in, vec_out, alpha, beta, trans)   y <- alpha*op(A)*x + beta*y with dense device vectors (not a mirror, see there)
     dbcsr_multivec(matrix, vecs_in, vecs_out, alpha, beta, trans)  Y <- alpha*op(A)*X + beta*Y with nrhs dense device vectors at once: A is read once
     dbcsr_rank_update(matrix, vecs_x, vecs_y, alpha, beta, trans)  A_IJ <- beta*A_IJ + alpha*X_I*op(Y_J) on the stored blocks only (not a mirror, see there)
+    dbcsr_get_block_diag(matrix)                                a new matrix of the diagonal blocks the matrix stores
+    dbcsr_invert_block_diag(matrix, check)                      every stored diagonal block <- its inverse, in place (not a mirror, see there)
 
 Same argument names and error behaviour; the work is done by the C-ABI engine (include/dbcsr_amd_mm.h, "Matrix algebra between
 multiplies") on the GPU, for float64, float32 and complex128 data.  One rank / one device here: of a distributed matrix trace, dot
@@ -521,3 +523,86 @@ def dbcsr_rank_update(matrix, vecs_x, vecs_y=None, alpha=1.0, beta=1.0, trans="T
                                         vecs_y.data_ptr() if n_cols and nrhs else None, n_cols, ldy, _z(beta), C.byref(d), st.ptr)
     if rc != 0:
         raise RuntimeError("dbcsr_amd_bcsr_rank_update failed (%d)" % rc)
+
+
+# ---- block diagonal --------------------------------------------------------------------------------------------------------------------------------
+BLOCK_INVERSE_MAX_DIM = 96   # the largest diagonal block dbcsr_invert_block_diag takes (include/dbcsr_amd_mm.h)
+_MAX_SIZES = {}   # (serial, version) of a block-size tensor -> its largest entry, as _FULL_SIZES holds the sums
+
+
+def _max_size(sizes):
+    key = (_serial(sizes), sizes._version)
+    n = _MAX_SIZES.get(key)
+    if n is None:
+        if len(_MAX_SIZES) > 256:
+            _MAX_SIZES.clear()
+        n = _MAX_SIZES[key] = int(sizes.max().item()) if sizes.numel() else 0
+    return n
+
+
+def dbcsr_get_block_diag(matrix, engine=None, stream=None):
+    """A new matrix of the diagonal blocks the matrix stores (dbcsr_get_block_diag(matrix, diag)): the matrix' block sizes, data type, name and symmetry;
+    exactly its stored diagonal blocks, in block-row order and packed, as bit-for-bit copies; a block row without a diagonal block has none in the result.
+    Any symmetry: a diagonal block is stored in full and taken as it is.  Square block structure (nblkrows == nblkcols and equal row / column block sizes,
+    else ValueError).  The matrix is only read: it keeps its index_stamp() and no saved plan is invalidated.  Synchronises once (the size of the result).
+    dbcsr_invert_block_diag of the result is the initial guess X0 = blockdiag(S)^-1 of a Hotelling / Newton-Schulz inverse, and
+    dbcsr_multivec(that, R) the block-Jacobi preconditioner Y <- blockdiag(A)^-1 R."""
+    name = "dbcsr_get_block_diag"
+    sym = _check_symmetry(name, matrix)
+    _check_square(name, matrix)
+    matrix.dtype_code
+    E = engine or default_engine()
+    st = StreamHandle(stream)
+    A = matrix
+    dev = A.row_p.device
+    n = A.nblkrows
+    a = A.desc()
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        row_p = torch.empty(n + 1, dtype=torch.int32, device=dev)
+        col_i = torch.empty(n, dtype=torch.int32, device=dev)
+        blk_p = torch.empty(n, dtype=torch.int64, device=dev)
+    nb, nz, md = C.c_int64(), C.c_int64(), C.c_int32()
+    rc = E.L.dbcsr_amd_bcsr_block_diag_count(E.h, C.byref(a), row_p.data_ptr(), col_i.data_ptr() if n else None, blk_p.data_ptr() if n else None,
+                                             C.byref(nb), C.byref(nz), C.byref(md), st.ptr)
+    if rc != 0:
+        raise RuntimeError("dbcsr_amd_bcsr_block_diag_count failed (%d)" % rc)
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        D = DbcsrMatrix(A.row_blk_size, A.col_blk_size, row_p, col_i[:nb.value].contiguous(), blk_p[:nb.value].contiguous(),
+                        torch.empty(nz.value, dtype=A.dtype, device=dev), A.name, symmetry=sym)
+    d = D.desc(out=True)
+    rc = E.L.dbcsr_amd_bcsr_block_diag_apply(E.h, A.dtype_code, C.byref(a), C.byref(d), st.ptr)
+    if rc != 0:
+        raise RuntimeError("dbcsr_amd_bcsr_block_diag_apply failed (%d)" % rc)
+    return D
+
+
+def dbcsr_invert_block_diag(matrix, check=True, engine=None, stream=None):
+    """Every diagonal block the matrix stores <- its inverse, in place, and nothing else.  NOT a mirror of a routine of the reference: it is what CP2K does
+    on the host with an iterator over the blocks and invmat (the initial guess of invert_Hotelling, the block-Jacobi preconditioners), and does not
+    claim a DBCSR name.  With D = dbcsr_get_block_diag(S), dbcsr_invert_block_diag(D) makes D the initial guess X0 = blockdiag(S)^-1 of a Hotelling /
+    Newton-Schulz inverse, and dbcsr_multivec(D, R) then is the block-Jacobi preconditioner Y <- blockdiag(A)^-1 R.
+    Blocks off the diagonal, the holes of an unpacked matrix and everything else of the data area keep their bits; no index array is written,
+    index_stamp() stays, a multiply with the matrix as operand afterwards reuses its plan.  Gauss-Jordan with partial pivoting in double / complex double
+    (float32: converted on load, rounded once on store); the same bits on every call, wherever the block lies.  Symmetry 'N', 'S', 'H': the stored full
+    diagonal block is inverted as a general matrix and nothing is symmetrised afterwards; 'A' / 'K': ValueError.  Square block structure, else
+    ValueError; a block size above 96: NotImplementedError; every refusal comes before any call of the library.
+    A singular block (a pivot column that is exactly zero, or all NaN) is not written at all and every other block is still inverted.  check=True:
+    returns (n_singular, first_singular_block_row), the row -1 when there is none -- one synchronisation.  check=False: returns None and nothing
+    synchronises (the first call for a block-size tensor synchronises once to learn the largest block size)."""
+    name = "dbcsr_invert_block_diag"
+    sym = _check_symmetry(name, matrix)
+    if sym in ("A", "K"):
+        raise ValueError("%s: not defined for an antisymmetric / antihermitian matrix (symmetry %r)" % (name, sym))
+    _check_square(name, matrix)
+    matrix.dtype_code
+    max_dim = _max_size(matrix.row_blk_size)
+    if max_dim > BLOCK_INVERSE_MAX_DIM:
+        raise NotImplementedError("%s: a block of %d (diagonal blocks of up to %d are inverted)" % (name, max_dim, BLOCK_INVERSE_MAX_DIM))
+    E = engine or default_engine()
+    st = StreamHandle(stream)
+    d = matrix.desc()   # (only the data area is written)
+    info = (C.c_int64 * 3)() if check else None
+    rc = E.L.dbcsr_amd_bcsr_block_diag_invert(E.h, matrix.dtype_code, C.byref(d), max_dim, info, st.ptr)
+    if rc != 0:
+        raise RuntimeError("dbcsr_amd_bcsr_block_diag_invert failed (%d)" % rc)
+    return (int(info[0]), int(info[1])) if check else None

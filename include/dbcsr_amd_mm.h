@@ -102,7 +102,7 @@ int dbcsr_amd_mm_symbolic_filtered(void* handle, libsmm_acc_data_t datatype, dou
  * Block norms left by a multiply: the exact-size, slab and class kernels of a FILTERED fp64 multiply (dbcsr_amd_mm_symbolic_filtered with filter_eps > 0)
  * leave every C block's squared norm behind, and a _filter_count on that C -- same data pointer, same block count -- uses them instead of a pass over C.
  * The engine forgets them in the next symbolic phase, numeric phase or filter count, and in every entry that writes a matrix's values (init_c, scale_window,
- * add_apply, the diagonal entries, set_diag, scale_by_vector, rank_update, fill_random, crop / filter apply, transpose, twin moves).  It cannot see a write
+ * add_apply, the diagonal entries, set_diag, scale_by_vector, rank_update, block_diag_apply / _invert, fill_random, crop / filter apply, transpose, twin moves).  It cannot see a write
  * made outside it: the norms are good only while nobody else writes C -- or frees it and allocates another matrix there -- between the numeric phase and
  * the filter. */
 int dbcsr_amd_bcsr_filter_count(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, double eps, int32_t* new_row_p,
@@ -433,6 +433,35 @@ int dbcsr_amd_bcsr_multivec(void* handle, libsmm_acc_data_t datatype, char trans
  *               write stays inside the blocks that the index names. */
 int dbcsr_amd_bcsr_rank_update(void* handle, libsmm_acc_data_t datatype, char trans, const double alpha[2], int nrhs, const void* x, int64_t n_x,
   int64_t ldx, const void* y, int64_t n_y, int64_t ldy, const double beta[2], dbcsr_amd_bcsr* a, void* stream);
+
+/* Block diagonal: dbcsr_get_block_diag of the reference, and the batched inversion of the diagonal blocks that CP2K does on the host with an iterator and
+ * invmat -- the initial guess X0 = blockdiag(S)^-1 of a Hotelling / Newton-Schulz inverse, and the block-Jacobi preconditioner blockdiag(A)^-1 that
+ * _multivec then applies.  Same types and answers as the algebra above (-10 for another type code; -1 for a null handle or matrix and for
+ * nblkrows != nblkcols).  A diagonal block is the block (r, r) the index names; of a stored triangle it is stored in full and taken as it is.  All three
+ * use buffers of their own (and the scan's scratch): no saved plan is touched, no work area of the symbolic phase is written.
+ *   _block_diag_count   the whole index of the matrix of the diagonal blocks m STORES, in block-row order and packed: dst_row_p [nblkrows + 1], dst_col_i /
+ *     dst_blk_p [nblkrows] (device; the first *nblks entries are written, blk_p the running sum of the block sizes), and on the host *nblks, *nze and
+ *     *max_dim, the largest dimension of such a block (0 when there is none).  A block row without a diagonal block has none in the result.  Synchronises
+ *     once, as _diag_count does.
+ *   _block_diag_apply   dst's diagonal blocks = src's diagonal blocks, bit for bit, found by both indices (dst: the index _block_diag_count made, data [nze]
+ *     allocated by the caller and not src's).  Reads src only at its diagonal blocks, writes dst only inside its blocks.  Asynchronous on stream.
+ *   _block_diag_invert  in place: every diagonal block m stores is replaced by its inverse; blocks off the diagonal, the holes of an unpacked matrix and
+ *     everything else of the data area keep their bits; no index array is written.  Gauss-Jordan with partial (row) pivoting on a copy of the block in
+ *     LDS, in double / complex double for all three types (real_4: converted on load, rounded once on store).  The pivot of a column is the largest |x|
+ *     (complex data: |re| + |im|) at or below the diagonal, the lowest row on ties, compared with > so that a NaN never wins.  The bits of an inverse depend
+ *     on the block's values, dimension and type alone -- not on where the block lies, on the alignment of the data area, on the other blocks or on the
+ *     call; no atomics on data.  A block with a pivot column that is exactly zero (or all NaN) is SINGULAR: it is not written at all, it is counted, and
+ *     every other block is still inverted.  A block that holds Inf or NaN gets no promise about its own values; the writes stay inside it.
+ *     max_dim is the caller's bound on the dimension of a diagonal block (it sizes the LDS of the launch): one wave inverts a block of up to 32, one
+ *     workgroup of 256 a block of 33 ... 96, both kinds in one call.  A diagonal block whose dimension exceeds max_dim (or that is not square) is SKIPPED:
+ *     left untouched and counted, never a fault.  info may be NULL: then nothing synchronises.  Otherwise (host; synchronises once) info[0] = the number
+ *     of singular blocks, info[1] = the first such block row or -1, info[2] = the number of skipped blocks.  -1 also for max_dim < 0; -11 for max_dim
+ *     above 96, the supported limit (96 x 97 complex doubles fill the LDS of a compute unit), with nothing launched; 0 with nothing written for an empty
+ *     matrix (info = {0, -1, 0}). */
+int dbcsr_amd_bcsr_block_diag_count(void* handle, const dbcsr_amd_bcsr* m, int32_t* dst_row_p, int32_t* dst_col_i, int64_t* dst_blk_p,
+  int64_t* nblks, int64_t* nze, int32_t* max_dim, void* stream);
+int dbcsr_amd_bcsr_block_diag_apply(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, dbcsr_amd_bcsr* dst, void* stream);
+int dbcsr_amd_bcsr_block_diag_invert(void* handle, libsmm_acc_data_t datatype, dbcsr_amd_bcsr* m, int max_dim, int64_t info[3], void* stream);
 
 /* Measurement helper (bench.py, roofline.fabric): what the L2 <-> Infinity-Cache fabric of the current device delivers, in TB/s -- a
  * plain streaming read of a 160 MB window by all CUs, and the block gather of the block-product dataflow (4232-byte blocks from

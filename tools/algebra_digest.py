@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The bits of the matrix algebra between multiplies (dbcsr_amd/operations.py; kernels of dbcsr_amd/csrc/mm_algebra.h, mm_multivec.h, mm_rank_update.h
-over the block walk of mm_block_walk.h): one line per case with the case's name and the SHA-256 of every output -- the index arrays and the whole
+"""The bits of the matrix algebra between multiplies (dbcsr_amd/operations.py; kernels of dbcsr_amd/csrc/mm_algebra.h, mm_multivec.h, mm_rank_update.h,
+mm_block_inverse.h over the block walk of mm_block_walk.h): one line per case with the case's name and the SHA-256 of every output -- the index arrays and the whole
 data area (holes included) of a matrix, a vector, the 8 or 16 bytes of a scalar.
 
     python tools/algebra_digest.py --out digest.txt
@@ -242,6 +242,12 @@ def run_type(cases, tname, dtype):
         else:
             ops.dbcsr_rank_update(A, x, None, 0.3, 0.5, "C" if is_z else "T", engine=eng)
         cases.add("%s rank_update" % tag, matrix_sha(A))
+        # the block diagonal: its copy, and every stored diagonal block inverted in place (blocks of 1 ... 70: the wave and the workgroup kernel)
+        A = make()
+        cases.add("%s get_block_diag" % tag, matrix_sha(ops.dbcsr_get_block_diag(A, engine=eng)))
+        singular = ops.dbcsr_invert_block_diag(A, engine=eng)
+        assert singular == (0, -1), singular
+        cases.add("%s invert_block_diag" % tag, matrix_sha(A))
 
 
 def main():

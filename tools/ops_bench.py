@@ -55,12 +55,23 @@ in every alternation:
 
     python tools/ops_bench.py --rank-update --alternations 7 --warmup 2 --mfma-tflops T --out profiles/rank_update.txt
 
+With --block-inverse only the block diagonal is timed (dbcsr_get_block_diag, dbcsr_invert_block_diag; kernels of dbcsr_amd/csrc/mm_block_inverse.h) on
+1424 diagonal blocks of 23 x 23 (the diagonal of config 2's product shape), 32, 64 and 96, float64, alternating: get_block_diag of a matrix with eight more
+blocks per block row, invert_block_diag without and with the check, dbcsr_scale of the block diagonal as the fixed cost of one launch, the device path
+get_block_diag + invert_block_diag(check=True), the host round trip it replaces (to_host, numpy.linalg.inv of the stack of diagonal blocks, upload,
+synchronise) and torch.linalg.inv on the (1424, n, n) device stack.  These rows are wall-clock times around a device synchronisation (the calls that
+answer on the host synchronise themselves), --reps calls per sample.  The condition: at 23 x 23 the device path is not slower than the host round trip in
+any alternation:
+
+    python tools/ops_bench.py --block-inverse --alternations 7 --warmup 2 --out profiles/block_inverse.txt
+
 A sample is `--reps` calls back to back between two device events, divided by reps.  Bytes are counted from the shapes: 8 * (elements read + elements
 written) of the data areas, index arrays left out.  Spread = (max - min) / median over the samples."""
 import argparse
 import ctypes as C
 import os
 import sys
+import time
 
 import numpy as np
 import torch
@@ -69,7 +80,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from dbcsr_amd import lib as L  # noqa: E402
 from dbcsr_amd.matrix import DbcsrMatrix, StreamHandle  # noqa: E402
 from dbcsr_amd.multiply import MultiplyEngine  # noqa: E402
-from dbcsr_amd.operations import dbcsr_add  # noqa: E402
+from dbcsr_amd.operations import dbcsr_add, dbcsr_get_block_diag, dbcsr_invert_block_diag, dbcsr_scale  # noqa: E402
 
 
 def matrix_of(mask, b, seed):
@@ -302,6 +313,100 @@ def rank_update(args, say, lines, rng, b, nb, st):
             f.write("\n".join(lines) + "\n")
 
 
+def sample_wall(fn, reps):
+    """ms per call by the host's clock, the device idle before and after (for calls that answer on the host)"""
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    return 1e3 * (time.perf_counter() - t0) / reps
+
+
+def block_inverse(args, say, lines, rng):
+    E = MultiplyEngine()
+    nb, extra = 1424, 8
+    t = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a), dtype=dt).cuda()
+    results = {}
+    for b in (23, 32, 64, 96):
+        # S: the diagonal blocks (uniform(-0.5, 0.5) + b / 2 on the diagonal: condition numbers of a few units, so that inverting the inverse again and
+        # again stays where it is) and `extra` blocks per block row off the diagonal
+        mask = np.zeros((nb, nb), bool)
+        mask[np.arange(nb), np.arange(nb)] = True
+        for r in range(nb):
+            mask[r, rng.choice(nb, extra, replace=False)] = True
+        S = matrix_of(mask, b, 10 + b)
+        rows, cols = np.nonzero(mask)
+        diag_at = np.flatnonzero(rows == cols)
+        view, at = S.data.view(-1, b, b), torch.as_tensor(diag_at, device="cuda")
+        view[at] = view[at] + 0.5 * b * torch.eye(b, dtype=torch.float64, device="cuda")
+        D = dbcsr_get_block_diag(S, engine=E)
+        keep = D.data.clone()
+        # the inverse is one: against torch on the host, block by block
+        assert dbcsr_invert_block_diag(D, engine=E) == (0, -1)
+        ref = np.linalg.inv(keep.view(nb, b, b).cpu().numpy())
+        err = float(np.max(np.abs(D.data.view(nb, b, b).cpu().numpy() - ref)) / np.max(np.abs(ref)))
+        say("%d blocks of %d x %d: max |device - numpy.linalg.inv| / max |inverse| = %.2e" % (nb, b, b, err))
+        if not err < 1e-12:
+            sys.exit("the block inverse is wrong: nothing is timed")
+        D.data.copy_(keep)
+
+        def host_round_trip():
+            rs, cs, row_p, col_i, blk_p, data = S.to_host()
+            r_of = np.repeat(np.arange(len(rs)), np.diff(row_p))
+            at = np.flatnonzero(r_of == col_i)
+            blocks = np.stack([data[blk_p[i]:blk_p[i] + b * b].reshape(b, b) for i in at])
+            inv = np.linalg.inv(blocks)
+            X = DbcsrMatrix(S.row_blk_size, S.col_blk_size, t(np.arange(nb + 1), torch.int32), t(np.arange(nb), torch.int32),
+                            t(np.arange(nb, dtype=np.int64) * b * b, torch.int64), torch.as_tensor(inv.reshape(-1)).cuda())
+            torch.cuda.synchronize()
+            return X
+
+        def device_path():
+            X = dbcsr_get_block_diag(S, engine=E)
+            dbcsr_invert_block_diag(X, check=True, engine=E)
+            return X
+
+        stack = keep.view(nb, b, b).clone()
+        run = {
+            "scale": lambda: dbcsr_scale(D, 0.9999, engine=E),
+            "get_block_diag": lambda: dbcsr_get_block_diag(S, engine=E),
+            "invert": lambda: dbcsr_invert_block_diag(D, check=False, engine=E),
+            "invert.check": lambda: dbcsr_invert_block_diag(D, check=True, engine=E),
+            "device path": device_path,
+        }
+        if b == 23:
+            run["host path"] = host_round_trip
+        try:
+            torch.linalg.inv(stack)
+            torch.cuda.synchronize()
+            run["torch.inv"] = lambda: torch.linalg.inv(stack)
+        except Exception as e:   # (recorded: the yardstick is optional)
+            say("torch.linalg.inv on the (%d, %d, %d) device stack does not work here: %s" % (nb, b, b, str(e).splitlines()[0][:120]))
+        times = {k: [] for k in run}
+        for step in range(args.warmup + args.alternations):
+            for k in run:
+                x = sample_wall(run[k], 1 if k == "host path" else args.reps)
+                if step >= args.warmup:
+                    times[k].append(x)
+        say("")
+        say("%d blocks of %d x %d (%.1f MB of diagonal blocks; S has %d blocks)" % (nb, b, b, 8e-6 * nb * b * b, S.nblks))
+        for k in run:
+            v = sorted(times[k])
+            med = v[len(v) // 2]
+            say("  %-15s median %8.4f ms  min %8.4f  max %8.4f  spread %5.1f %%   samples: %s"
+                % (k, med, v[0], v[-1], 100 * (v[-1] - v[0]) / med, " ".join("%.4f" % x for x in times[k])))
+        results[b] = times
+        del S, D, keep, stack
+    say("")
+    say("condition: at 23 x 23 the device path (get_block_diag + invert_block_diag(check=True)) is not slower than the host round trip in any alternation")
+    r = sorted(x / z for x, z in zip(results[23]["device path"], results[23]["host path"]))
+    say("  device path / host path  %.4f ... %.4f   the condition %s" % (r[0], r[-1], "holds" if r[-1] <= 1.0 else "FAILS"))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=32768)
@@ -315,6 +420,7 @@ def main():
     ap.add_argument("--matvec", action="store_true", help="only the matrix-vector product, its yardsticks and the sums its passes are made from")
     ap.add_argument("--multivec", action="store_true", help="only the matrix times several dense vectors and its yardsticks")
     ap.add_argument("--rank-update", action="store_true", help="only the rank-k update on the stored pattern and its yardsticks")
+    ap.add_argument("--block-inverse", action="store_true", help="only the block diagonal: get_block_diag, invert_block_diag and what they replace")
     ap.add_argument("--mfma-tflops", type=float, default=None, help="with --rank-update: the fp64 MFMA figure bench.py --full measured in the same session")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     args = ap.parse_args()
@@ -333,6 +439,8 @@ def main():
         return multivec(args, say, lines, rng, b, nb, st)
     if args.rank_update:
         return rank_update(args, say, lines, rng, b, nb, st)
+    if args.block_inverse:
+        return block_inverse(args, say, lines, rng)
     only = ("norm", "norm.T", "matvec.N", "matvec.T", "matvec.S", "gersh.N", "colnorm", "gersh.S") if args.matvec else None
     # the same-pattern pair
     mask = rng.random((nb, nb)) < args.fill_flat
