@@ -1,7 +1,8 @@
 // mm_engine_algebra.h -- part of mm_engine.hip (included inside extern "C", after mm_engine_ops.h): the C-ABI operations between multiplies --
 // dbcsr_amd_bcsr_add_count / _add_apply, the pieces of dbcsr_add_on_diag (dbcsr_amd_bcsr_diag_count / _diag_fill / _diag_shift), dbcsr_amd_bcsr_trace,
 // _dot, _norm2, and the norms and vectors: dbcsr_amd_bcsr_maxabs, _row_sums, _col_sums, _gershgorin, _get_diag, _set_diag, _scale_by_vector, _matvec, _multivec, _rank_update,
-// and the block diagonal: dbcsr_amd_bcsr_block_diag_count / _apply / _invert.  Kernels: mm_algebra.h, mm_multivec.h, mm_rank_update.h, mm_block_inverse.h. The reductions, the diagonal pieces, the same-pattern add and the norms and vectors use buffers of their own (Engine::alg_*) and the
+// the block diagonal: dbcsr_amd_bcsr_block_diag_count / _apply / _invert, and the dense conversion: dbcsr_amd_bcsr_to_dense / _from_dense_apply /
+// _from_dense_count.  Kernels: mm_algebra.h, mm_multivec.h, mm_rank_update.h, mm_block_inverse.h, mm_dense.h. The reductions, the diagonal pieces, the same-pattern add and the norms and vectors use buffers of their own (Engine::alg_*) and the
 // scan's scratch, which no saved plan depends on (the checksum uses it the same way): they do NOT invalidate the plan.  The union add borrows the
 // symbolic phase's bitmaps and prefix arrays and invalidates it, as filter and crop do.
 #ifndef DBCSR_AMD_MM_ENGINE_ALGEBRA_H
@@ -485,7 +486,7 @@ int dbcsr_amd_bcsr_gershgorin(void* handle, libsmm_acc_data_t datatype, const db
     if (m->index_stamp != 0) {
       Engine::AlgLen& k = E->alg_len[E->alg_len_next];
       E->alg_len_next = (E->alg_len_next + 1) % Engine::kAlgLens;
-      k.rs = m->row_blk_size, k.cs = m->col_blk_size, k.stamp = m->index_stamp, k.nbr = m->nblkrows, k.nbc = m->nblkcols, k.rows = n;
+      k.rs = m->row_blk_size, k.cs = m->col_blk_size, k.stamp = m->index_stamp, k.nbr = m->nblkrows, k.nbc = m->nblkcols, k.rows = n, k.cols = -1;
     }
   }
   if (n <= 0) return 0;
@@ -824,6 +825,147 @@ int dbcsr_amd_bcsr_block_diag_invert(void* handle, libsmm_acc_data_t datatype, d
     info[2] = E->host_scalars[2];
   }
   return check(hipGetLastError(), "dbcsr_amd_bcsr_block_diag_invert", __FILE__, __LINE__);
+}
+// ---- dense conversion (kernels: mm_dense.h) -----------------------------------------------------------------------------------------------------------------
+// Everything here works in Engine::alg_i32 / alg_i64 and the scan's scratch: no entry invalidates the plan or writes a work area of the symbolic phase.
+extern "C++" {
+// The full row and column counts of m's block sizes, which only the device knows: remembered per set of block sizes as dbcsr_amd_bcsr_gershgorin remembers
+// its row count (same size arrays, same non-zero index_stamp), fetched otherwise -- then, and only then, the call synchronises.
+static int dense_lengths(Engine* E, hipStream_t st, const dbcsr_amd_bcsr* m, const int64_t* roff, const int64_t* coff, int64_t* rows, int64_t* cols) {
+  if (m->index_stamp != 0)
+    for (const Engine::AlgLen& k : E->alg_len)
+      if (k.stamp == m->index_stamp && k.rs == m->row_blk_size && k.cs == m->col_blk_size && k.nbr == m->nblkrows && k.nbc == m->nblkcols && k.cols >= 0) {
+        *rows = k.rows, *cols = k.cols;
+        return 0;
+      }
+  ACC_CHECK(hipMemcpyAsync(E->host_scalars + 6, roff + m->nblkrows, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  ACC_CHECK(hipMemcpyAsync(E->host_scalars + 7, coff + m->nblkcols, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  ACC_CHECK(hipStreamSynchronize(st));
+  *rows = E->host_scalars[6], *cols = E->host_scalars[7];
+  if (m->index_stamp != 0) {
+    Engine::AlgLen& k = E->alg_len[E->alg_len_next];
+    E->alg_len_next = (E->alg_len_next + 1) % Engine::kAlgLens;
+    k.rs = m->row_blk_size, k.cs = m->col_blk_size, k.stamp = m->index_stamp, k.nbr = m->nblkrows, k.nbc = m->nblkcols, k.rows = *rows, k.cols = *cols;
+  }
+  return 0;
+}
+
+// what the three entries ask of a window: 0 fine, -1 refused
+static inline int dense_window_args(const void* dense, int64_t n_rows, int64_t n_cols, int64_t ld, int col_major) {
+  if (n_rows < 0 || n_cols < 0 || ld < (col_major ? n_rows : n_cols)) return -1;
+  if (n_rows > 0 && n_cols > 0 && !dense) return -1;   // (a null tensor: only with an empty window)
+  return 0;
+}
+
+// block columns per workgroup of dense_gather: about 8192 elements of the window, at most 64 tiles
+static inline int dense_group(int64_t n_rows, int64_t n_cols, int nbr, int nbc) {
+  const int64_t tile = std::max<int64_t>(1, (n_rows / nbr) * (n_cols / nbc));
+  return (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(8192 / tile, 64), nbc));
+}
+
+template <typename T>
+static void dense_gather_launch(hipStream_t st, const dbcsr_amd_bcsr* m, const int64_t* roff, const int64_t* coff, int G, int NG, int kind, int col_major,
+                                void* dense, int64_t ld) {
+  hipLaunchKernelGGL((dense_gather<T>), dim3((unsigned)((int64_t)m->nblkrows * NG)), dim3(256), 0, st, m->row_p, m->col_i, m->blk_p,
+                     static_cast<const T*>(m->data), m->row_blk_size, m->col_blk_size, roff, coff, m->nblkrows, m->nblkcols, G, NG, kind, col_major,
+                     aligned16(m->data), static_cast<T*>(dense), ld);
+}
+
+template <typename T>
+static void dense_scatter_launch(hipStream_t st, dbcsr_amd_bcsr* m, const int64_t* roff, const int64_t* coff, int S, int col_major, const void* dense,
+                                 int64_t ld) {
+  hipLaunchKernelGGL((dense_scatter<T>), dim3((unsigned)((int64_t)m->nblkrows * S)), dim3(256), 0, st, m->row_p, m->col_i, m->blk_p,
+                     static_cast<T*>(m->data), m->row_blk_size, m->col_blk_size, roff, coff, m->nblkrows, S, col_major, aligned16(m->data),
+                     static_cast<const T*>(dense), ld);
+}
+
+template <typename T>
+static void dense_norms_launch(hipStream_t st, const void* dense, int64_t ld, int col_major, const int* rs, const int* cs, const int64_t* roff,
+                               const int64_t* coff, int nbr, int nbc, int64_t nt, int64_t n_rows, int64_t n_cols, double eps2, int* keep, int* nze) {
+  hipLaunchKernelGGL((dense_block_norms<T>), grid_for(nt * 64), dim3(256), 0, st, static_cast<const T*>(dense), ld, col_major, rs, cs, roff, coff, nbr, nbc,
+                     nt, n_rows, n_cols, eps2, keep, nze);
+}
+}  // extern "C++"
+
+int dbcsr_amd_bcsr_to_dense(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, int kind, void* dense, int64_t n_rows, int64_t n_cols,
+                            int64_t ld, int col_major, void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E || !m || kind < -1 || kind > 3 || (kind >= 0 && m->nblkrows != m->nblkcols)) return -1;
+  if (dense_window_args(dense, n_rows, n_cols, ld, col_major)) return -1;
+  if (!algebra_type(datatype)) return -10;
+  hipStream_t st = stream_of(stream);
+  const int64_t *roff = nullptr, *coff = nullptr;
+  int64_t rows = 0, cols = 0;
+  if (vector_offsets(E, st, m, &roff, &coff) || dense_lengths(E, st, m, roff, coff, &rows, &cols)) return -1;
+  if (rows != n_rows || cols != n_cols) return -1;
+  if (n_rows == 0 || n_cols == 0) return 0;
+  const int G = dense_group(n_rows, n_cols, m->nblkrows, m->nblkcols), NG = (m->nblkcols + G - 1) / G;
+  if ((int64_t)m->nblkrows * NG > INT32_MAX) return -1;   // (the grid)
+  DBCSR_AMD_BY_TYPE(dense_gather_launch, st, m, roff, coff, G, NG, kind, col_major ? 1 : 0, dense, ld);
+  return check(hipGetLastError(), "dbcsr_amd_bcsr_to_dense", __FILE__, __LINE__);
+}
+
+int dbcsr_amd_bcsr_from_dense_apply(void* handle, libsmm_acc_data_t datatype, const void* dense, int64_t n_rows, int64_t n_cols, int64_t ld, int col_major,
+                                    dbcsr_amd_bcsr* m, void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E || !m) return -1;
+  if (dense_window_args(dense, n_rows, n_cols, ld, col_major)) return -1;
+  if (!algebra_type(datatype)) return -10;
+  hipStream_t st = stream_of(stream);
+  const int64_t *roff = nullptr, *coff = nullptr;
+  int64_t rows = 0, cols = 0;
+  if (vector_offsets(E, st, m, &roff, &coff) || dense_lengths(E, st, m, roff, coff, &rows, &cols)) return -1;
+  if (rows != n_rows || cols != n_cols) return -1;
+  engine_writes_values(E);
+  if (n_rows == 0 || n_cols == 0 || m->nblks == 0) return 0;
+  const int S = algebra_split(m->nblkrows, m->nblks);
+  if ((int64_t)m->nblkrows * S > INT32_MAX) return -1;   // (the grid)
+  DBCSR_AMD_BY_TYPE(dense_scatter_launch, st, m, roff, coff, S, col_major ? 1 : 0, dense, ld);
+  return check(hipGetLastError(), "dbcsr_amd_bcsr_from_dense_apply", __FILE__, __LINE__);
+}
+
+int dbcsr_amd_bcsr_from_dense_count(void* handle, libsmm_acc_data_t datatype, const void* dense, int64_t n_rows, int64_t n_cols, int64_t ld, int col_major,
+                                    const int32_t* row_blk_size, const int32_t* col_blk_size, int nblkrows, int nblkcols, double eps, int32_t* dst_row_p,
+                                    int32_t* dst_col_i, int64_t* dst_blk_p, int64_t* nblks, int64_t* nze, void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E || !dst_row_p || !nblks || !nze || nblkrows < 0 || nblkcols < 0 || (nblkrows > 0 && !row_blk_size) || (nblkcols > 0 && !col_blk_size)) return -1;
+  if (!(eps >= 0.0)) return -1;   // (negative, or NaN)
+  if (dense_window_args(dense, n_rows, n_cols, ld, col_major)) return -1;
+  if (!algebra_type(datatype)) return -10;
+  *nblks = *nze = 0;
+  const int64_t nt = (int64_t)nblkrows * nblkcols;
+  if (nt > INT32_MAX - 8 || (nt > 0 && (!dst_col_i || !dst_blk_p))) return -1;
+  hipStream_t st = stream_of(stream);
+  dbcsr_amd_bcsr sizes = {};   // (vector_offsets reads the block sizes and their counts)
+  sizes.nblkrows = nblkrows, sizes.nblkcols = nblkcols, sizes.row_blk_size = row_blk_size, sizes.col_blk_size = col_blk_size;
+  const size_t noff = (size_t)nblkrows + (size_t)nblkcols + 2;
+  if (E->alg_i32.ensure(4 + 3 * (size_t)nt + 2) || E->alg_i64.ensure(8 + noff + (size_t)nt + 2)) return -1;
+  const int64_t *roff = nullptr, *coff = nullptr;
+  if (vector_offsets(E, st, &sizes, &roff, &coff)) return -1;   // (in alg_i64 behind its eight scalars: the ensure above holds it)
+  int* keep = E->alg_i32.p + 4;
+  int* tile_nze = keep + nt;
+  int* pos = tile_nze + nt;
+  int64_t* off = E->alg_i64.p + 8 + noff;
+  // The block-size sums are known on the device alone.  dense_block_norms compares them with the window itself and reads nothing of dense when they
+  // differ (every tile is then dropped), so the one synchronisation at the end brings the sums along with the counts.
+  if (nt > 0) {
+    DBCSR_AMD_BY_TYPE(dense_norms_launch, st, dense, ld, col_major ? 1 : 0, row_blk_size, col_blk_size, roff, coff, nblkrows, nblkcols, nt, n_rows, n_cols,
+                      eps * eps, keep, tile_nze);
+    if (exclusive_scan<int32_t>(E, keep, nt, pos, E->alg_i64.p + 0, true, st)) return -1;
+    if (exclusive_scan<int64_t>(E, tile_nze, nt, off, E->alg_i64.p + 1, false, st)) return -1;
+    hipLaunchKernelGGL(dense_emit, grid_for(nt), dim3(256), 0, st, keep, pos, off, nblkrows, nblkcols, nt, dst_row_p, dst_col_i, dst_blk_p);
+  } else {
+    ACC_CHECK(hipMemsetAsync(dst_row_p, 0, sizeof(int32_t) * ((size_t)nblkrows + 1), st));
+    ACC_CHECK(hipMemsetAsync(E->alg_i64.p, 0, 2 * sizeof(int64_t), st));
+  }
+  ACC_CHECK(hipMemcpyAsync(E->host_scalars, E->alg_i64.p, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  ACC_CHECK(hipMemcpyAsync(E->host_scalars + 6, roff + nblkrows, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  ACC_CHECK(hipMemcpyAsync(E->host_scalars + 7, coff + nblkcols, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  ACC_CHECK(hipStreamSynchronize(st));
+  if (E->host_scalars[6] != n_rows || E->host_scalars[7] != n_cols) return -1;
+  *nblks = E->host_scalars[0];
+  *nze = E->host_scalars[1];
+  return check(hipGetLastError(), "dbcsr_amd_bcsr_from_dense_count", __FILE__, __LINE__);
 }
 #undef DBCSR_AMD_BY_TYPE
 

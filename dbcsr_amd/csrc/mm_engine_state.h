@@ -141,6 +141,7 @@ struct Engine {
     uint64_t stamp = 0;
     int nbr = 0, nbc = 0;
     int64_t rows = 0;
+    int64_t cols = -1;   // the full column count, where an entry of the dense conversion fetched it (-1: not known)
   };
   static constexpr int kAlgLens = 8;
   AlgLen alg_len[kAlgLens];

@@ -17,6 +17,9 @@
     dbcsr_rank_update(matrix, vecs_x, vecs_y, alpha, beta, trans)  A_IJ <- beta*A_IJ + alpha*X_I*op(Y_J) on the stored blocks only (not a mirror, see there)
     dbcsr_get_block_diag(matrix)                                a new matrix of the diagonal blocks the matrix stores
     dbcsr_invert_block_diag(matrix, check)                      every stored diagonal block <- its inverse, in place (not a mirror, see there)
+    dbcsr_to_dense(matrix, out)                                 the full matrix as a dense device tensor (dbcsr_to_dense_local / copy_dbcsr_to_fm)
+    dbcsr_from_dense(dense, matrix)                             the stored blocks <- the dense tensor's elements (copy_fm_to_dbcsr, keep_sparsity)
+    dbcsr_create_from_dense(dense, row_blk_size, col_blk_size, eps)  a new matrix of the blocks of a dense tensor that the block filter keeps
 
 Same argument names and error behaviour; the work is done by the C-ABI engine (include/dbcsr_amd_mm.h, "Matrix algebra between
 multiplies") on the GPU, for float64, float32 and complex128 data.  One rank / one device here: of a distributed matrix trace, dot
@@ -26,7 +29,7 @@ import math
 
 import torch
 
-from .matrix import DbcsrMatrix, StreamHandle, _serial
+from .matrix import DbcsrMatrix, StreamHandle, _dtype_code, _serial
 from .multiply import _z, default_engine
 
 _SYMMETRIES = ("N", "S", "A", "H", "K")
@@ -606,3 +609,161 @@ def dbcsr_invert_block_diag(matrix, check=True, engine=None, stream=None):
     if rc != 0:
         raise RuntimeError("dbcsr_amd_bcsr_block_diag_invert failed (%d)" % rc)
     return (int(info[0]), int(info[1])) if check else None
+
+
+# ---- dense conversion ------------------------------------------------------------------------------------------------------------------------------
+def _check_dense(name, dtype, device, dense, n_rows, n_cols, what="dense"):
+    """a 2-D device tensor of (n_rows, n_cols) elements of `dtype` whose rows or whose columns are contiguous: checked before any call of the library.
+    Returns (ld, col_major): strides (ld, 1) with ld >= n_cols -- torch's layout, or a column slice of a wider tensor -- or (1, ld) with ld >= n_rows,
+    column by column as a Fortran full matrix is (t.T of a contiguous tensor)."""
+    if not isinstance(dense, torch.Tensor):
+        raise TypeError("%s: %s must be a torch tensor" % (name, what))
+    if dense.dtype != dtype:
+        raise TypeError("%s: %s has data type %r, expected %r" % (name, what, dense.dtype, dtype))
+    if dense.device != device:
+        raise ValueError("%s: %s is not on the matrix' device" % (name, what))
+    if dense.dim() != 2 or tuple(dense.shape) != (n_rows, n_cols):
+        raise ValueError("%s: %s must be a 2-D tensor of shape (%d, %d), got %r" % (name, what, n_rows, n_cols, tuple(dense.shape)))
+    s0, s1 = dense.stride()
+    rows_ok, cols_ok = n_cols <= 1 or s1 == 1, n_rows <= 1 or s0 == 1   # (the stride of a dimension of one element, or of none, says nothing)
+    if rows_ok and (n_rows <= 1 or s0 >= max(n_cols, 1)):
+        return (s0 if n_rows > 1 else max(n_cols, 1)), 0
+    if cols_ok and (n_cols <= 1 or s1 >= max(n_rows, 1)):
+        return (s1 if n_cols > 1 else max(n_rows, 1)), 1
+    if not rows_ok and not cols_ok:
+        raise ValueError("%s: %s must have stride(1) == 1 (row by row) or stride(0) == 1 (column by column), got strides %r" % (name, what, (s0, s1)))
+    raise ValueError("%s: %s has strides %r: the stride between its rows (columns) is below the %d columns (%d rows) of one" % (name, what, (s0, s1), n_cols, n_rows))
+
+
+def _dense_overlaps(dense, n_rows, n_cols, ld, col_major, data):
+    return _overlaps(dense, n_cols, ld, n_rows, data) if col_major else _overlaps(dense, n_rows, ld, n_cols, data)
+
+
+def dbcsr_to_dense(matrix, out=None, engine=None, stream=None):
+    """The full (n_rows, n_cols) matrix as a dense device tensor (dbcsr_to_dense_local; CP2K's copy_dbcsr_to_fm), without leaving the device: what
+    torch.linalg.eigh / cholesky / svd, a dense Rayleigh-Ritz step or a comparison with a dense matrix take.  The stored blocks are at their places as
+    bit-for-bit copies, every other element is +0.0.  A stored triangle is expanded with the reading of the desymmetrized operands of a multiply: where
+    (r, c) is not stored and (c, r) is, the tile is that block's twin -- 'S' its transpose, 'A' minus its transpose, 'H' its conjugate transpose, 'K' minus
+    its conjugate transpose (sign flips: exact); diagonal blocks are taken in full as stored, nothing is symmetrised.
+    out=None allocates a contiguous row-by-row tensor on the matrix' device and stream.  Otherwise out is a 2-D device tensor of the matrix' data type and
+    that shape with strides (ld, 1), ld >= n_cols -- torch's layout, or a column slice of a wider tensor -- or (1, ld), ld >= n_rows -- column by column, what
+    a Fortran full matrix is: t.T of a contiguous tensor.  Every element of the window is written exactly once per call, whatever out held; nothing outside
+    it is written: the padding between the window and ld keeps its bits.  out must not overlap matrix.data (ValueError).  The matrix is only read: it keeps
+    its index_stamp() and no saved plan is touched.  float64, float32 and complex128; packed and unpacked matrices.  Asynchronous on the stream (the first
+    call for a set of block sizes synchronises once to learn their sums), the same bits on every call; every refusal comes before any call of the
+    library.  Returns out."""
+    name = "dbcsr_to_dense"
+    sym = _check_symmetry(name, matrix)
+    matrix.dtype_code
+    kind = -1
+    if sym != "N":
+        kind = matrix.symmetry_kind()
+        _check_square(name, matrix)
+    n_rows, n_cols = _full_size(matrix.row_blk_size), _full_size(matrix.col_blk_size)
+    ld, col_major = max(n_cols, 1), 0
+    if out is not None:
+        ld, col_major = _check_dense(name, matrix.dtype, matrix.row_p.device, out, n_rows, n_cols, "out")
+        if _dense_overlaps(out, n_rows, n_cols, ld, col_major, matrix.data):
+            raise ValueError("%s: out overlaps the matrix' data area" % name)
+    E = engine or default_engine()
+    st = StreamHandle(stream)
+    if out is None:
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            out = torch.empty((n_rows, n_cols), dtype=matrix.dtype, device=matrix.row_p.device)
+    d = matrix.desc()
+    rc = E.L.dbcsr_amd_bcsr_to_dense(E.h, matrix.dtype_code, C.byref(d), kind, out.data_ptr() if n_rows and n_cols else None, n_rows, n_cols, ld, col_major,
+                                     st.ptr)
+    if rc != 0:
+        raise RuntimeError("dbcsr_amd_bcsr_to_dense failed (%d)" % rc)
+    return out
+
+
+def dbcsr_from_dense(dense, matrix, engine=None, stream=None):
+    """Every block the matrix stores <- the dense tensor's elements at its place, bit for bit, and nothing else (CP2K's copy_fm_to_dbcsr with keep_sparsity):
+    the way back from a dense step -- eigenvectors, a Cholesky factor, a dense guess -- onto the pattern the matrix has.  dense: a 2-D device tensor of the
+    matrix' data type and full shape, in one of dbcsr_to_dense's two layouts.  The pattern never changes: no index array is written, index_stamp() stays, a
+    multiply with the matrix as operand afterwards reuses its plan; the holes of an unpacked matrix and everything around the blocks keep their bits; block
+    norms a multiply announced are forgotten.  No symmetry is applied: of a stored triangle the blocks the matrix stores are taken from where they lie, the
+    other triangle of dense is not read.  dense must not overlap matrix.data (ValueError).  Asynchronous on the stream as dbcsr_to_dense is; every refusal
+    comes before any call of the library.  Returns matrix."""
+    name = "dbcsr_from_dense"
+    sym = _check_symmetry(name, matrix)
+    matrix.dtype_code
+    if sym != "N":
+        matrix.symmetry_kind()
+        _check_square(name, matrix)
+    n_rows, n_cols = _full_size(matrix.row_blk_size), _full_size(matrix.col_blk_size)
+    ld, col_major = _check_dense(name, matrix.dtype, matrix.row_p.device, dense, n_rows, n_cols)
+    if _dense_overlaps(dense, n_rows, n_cols, ld, col_major, matrix.data):
+        raise ValueError("%s: dense overlaps the matrix' data area" % name)
+    E = engine or default_engine()
+    st = StreamHandle(stream)
+    d = matrix.desc()   # (only the data area is written)
+    rc = E.L.dbcsr_amd_bcsr_from_dense_apply(E.h, matrix.dtype_code, dense.data_ptr() if n_rows and n_cols else None, n_rows, n_cols, ld, col_major,
+                                             C.byref(d), st.ptr)
+    if rc != 0:
+        raise RuntimeError("dbcsr_amd_bcsr_from_dense_apply failed (%d)" % rc)
+    return matrix
+
+
+def _block_sizes(name, what, sizes, device):
+    """block sizes as the matrices hold them: a 1-D int32 tensor on the device (a tensor that already is one is taken as it is)"""
+    if isinstance(sizes, torch.Tensor) and sizes.dtype == torch.int32 and sizes.device == device and sizes.dim() == 1 and sizes.is_contiguous():
+        return sizes
+    t = torch.as_tensor(sizes)
+    if t.dim() != 1 or t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise TypeError("%s: %s must be a 1-D sequence of integers" % (name, what))
+    if t.numel() and int(t.min()) < 0:
+        raise ValueError("%s: %s has a negative block size" % (name, what))
+    return t.to(dtype=torch.int32).contiguous().to(device)
+
+
+def dbcsr_create_from_dense(dense, row_blk_size, col_blk_size, eps=0.0, name="", engine=None, stream=None):
+    """A new packed matrix without symmetry that holds the blocks of the dense device tensor which the block filter would keep: a block of the structure
+    row_blk_size x col_blk_size is dropped iff ||blk||_F^2 < eps^2 (dbcsr_filter's rule: a block whose norm is NaN stays; eps = 0.0 keeps every block, a
+    full pattern).  The index is sorted and packed -- block columns ascending inside a block row, blk_p the running sum of the block sizes -- and the
+    blocks are bit-for-bit copies.  dense: a 2-D device tensor (float64, float32 or complex128) in one of dbcsr_to_dense's two layouts, whose shape is the
+    sums of the block sizes (ValueError otherwise); the block sizes: int32 device tensors as the matrices hold them (taken as they are), or any sequence of
+    integers.  Norms summed in double in a fixed order: the same pattern and bits on every call.  Synchronises once (the size of the result); every
+    refusal comes before any call of the library."""
+    fn = "dbcsr_create_from_dense"
+    if not isinstance(dense, torch.Tensor):
+        raise TypeError("%s: dense must be a torch tensor" % fn)
+    code = _dtype_code(dense.dtype)
+    eps = float(eps)
+    if not eps >= 0:   # (a NaN compares false)
+        raise ValueError("%s: eps must be >= 0, got %r" % (fn, eps))
+    if dense.dim() != 2:
+        raise ValueError("%s: dense must be a 2-D tensor" % fn)
+    if dense.device.type != "cuda":
+        raise ValueError("%s: dense is not on a GPU" % fn)
+    dev = dense.device
+    rs, cs = _block_sizes(fn, "row_blk_size", row_blk_size, dev), _block_sizes(fn, "col_blk_size", col_blk_size, dev)
+    n_rows, n_cols = _full_size(rs), _full_size(cs)
+    if tuple(dense.shape) != (n_rows, n_cols):
+        raise ValueError("%s: dense has shape %r, the block sizes sum to (%d, %d)" % (fn, tuple(dense.shape), n_rows, n_cols))
+    ld, col_major = _check_dense(fn, dense.dtype, dev, dense, n_rows, n_cols)
+    nbr, nbc = int(rs.numel()), int(cs.numel())
+    nt = nbr * nbc
+    if nt > 2 ** 31 - 9:
+        raise ValueError("%s: a block structure of %d x %d blocks" % (fn, nbr, nbc))
+    E = engine or default_engine()
+    st = StreamHandle(stream)
+    ptr = dense.data_ptr() if n_rows and n_cols else None
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        row_p = torch.empty(nbr + 1, dtype=torch.int32, device=dev)
+        col_i = torch.empty(nt, dtype=torch.int32, device=dev)
+        blk_p = torch.empty(nt, dtype=torch.int64, device=dev)
+    nb, nz = C.c_int64(), C.c_int64()
+    rc = E.L.dbcsr_amd_bcsr_from_dense_count(E.h, code, ptr, n_rows, n_cols, ld, col_major, rs.data_ptr() if nbr else None, cs.data_ptr() if nbc else None,
+                                             nbr, nbc, float(eps), row_p.data_ptr(), col_i.data_ptr() if nt else None, blk_p.data_ptr() if nt else None,
+                                             C.byref(nb), C.byref(nz), st.ptr)
+    if rc != 0:
+        raise RuntimeError("dbcsr_amd_bcsr_from_dense_count failed (%d)" % rc)
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        M = DbcsrMatrix(rs, cs, row_p, col_i[:nb.value].clone(), blk_p[:nb.value].clone(), torch.empty(nz.value, dtype=dense.dtype, device=dev), name)
+    d = M.desc()
+    rc = E.L.dbcsr_amd_bcsr_from_dense_apply(E.h, code, ptr, n_rows, n_cols, ld, col_major, C.byref(d), st.ptr)
+    if rc != 0:
+        raise RuntimeError("dbcsr_amd_bcsr_from_dense_apply failed (%d)" % rc)
+    return M

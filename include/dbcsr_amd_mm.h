@@ -102,7 +102,7 @@ int dbcsr_amd_mm_symbolic_filtered(void* handle, libsmm_acc_data_t datatype, dou
  * Block norms left by a multiply: the exact-size, slab and class kernels of a FILTERED fp64 multiply (dbcsr_amd_mm_symbolic_filtered with filter_eps > 0)
  * leave every C block's squared norm behind, and a _filter_count on that C -- same data pointer, same block count -- uses them instead of a pass over C.
  * The engine forgets them in the next symbolic phase, numeric phase or filter count, and in every entry that writes a matrix's values (init_c, scale_window,
- * add_apply, the diagonal entries, set_diag, scale_by_vector, rank_update, block_diag_apply / _invert, fill_random, crop / filter apply, transpose, twin moves).  It cannot see a write
+ * add_apply, the diagonal entries, set_diag, scale_by_vector, rank_update, block_diag_apply / _invert, from_dense_apply, fill_random, crop / filter apply, transpose, twin moves).  It cannot see a write
  * made outside it: the norms are good only while nobody else writes C -- or frees it and allocates another matrix there -- between the numeric phase and
  * the filter. */
 int dbcsr_amd_bcsr_filter_count(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, double eps, int32_t* new_row_p,
@@ -462,6 +462,38 @@ int dbcsr_amd_bcsr_block_diag_count(void* handle, const dbcsr_amd_bcsr* m, int32
   int64_t* nblks, int64_t* nze, int32_t* max_dim, void* stream);
 int dbcsr_amd_bcsr_block_diag_apply(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, dbcsr_amd_bcsr* dst, void* stream);
 int dbcsr_amd_bcsr_block_diag_invert(void* handle, libsmm_acc_data_t datatype, dbcsr_amd_bcsr* m, int max_dim, int64_t info[3], void* stream);
+
+/* Dense conversion: dbcsr_to_dense_local of the reference and CP2K's copy_dbcsr_to_fm / copy_fm_to_dbcsr(keep_sparsity), between a matrix and a dense
+ * device tensor, without leaving the device.  `dense` is the window [n_rows, n_cols] of elements of the data type, element (i, j) at i * ld + j
+ * (col_major 0: row by row, as a torch tensor or a column slice of a wider one; ld >= n_cols) or at i + j * ld (col_major != 0: column by column, as a
+ * Fortran full matrix; ld >= n_rows).  Offsets into it are formed in 64 bits.  Same types as the algebra above (-10 for another type code).  -1 for a null
+ * handle or matrix, a negative n_rows / n_cols, an ld below the window's contiguous extent, n_rows / n_cols that are not the sums of the row / column block
+ * sizes, and a null dense with a window that has elements (a null dense is legal with an empty window: 0, nothing written).  The sums are known on the
+ * device alone: _to_dense and _from_dense_apply remember them per set of block sizes (same size arrays and the same non-zero index_stamp) and synchronise
+ * once when they meet a set they do not know -- otherwise they are asynchronous on stream and synchronise nothing.  All three work in buffers of the
+ * algebra (and the scan's scratch): no saved plan is touched, no work area of the symbolic phase is written.  No atomics on data; the same bits on every
+ * call.  The tensor must not overlap the data area of m (the caller's contract, as for _rank_update).
+ *   _to_dense          every element of the window is written exactly once: a stored block at its place, bit for bit, +0.0 everywhere else; nothing outside
+ *     the window is written (the padding between the window's extent and ld keeps its bits).  kind -1: the stored blocks only.  kind 0 ... 3 (S A H K; any
+ *     other kind, or nblkrows != nblkcols: -1): a stored triangle is expanded as _desymmetrized does -- where (r, c) is not stored and (c, r) is, the tile
+ *     is the twin of that block (transposed; bit 0 of kind negates, bit 1 conjugates: sign flips, exact); a diagonal block is taken in full as stored.
+ *     m is only read.
+ *   _from_dense_apply  every block the index of m names <- the window's elements at its place, bit for bit, and nothing else: no index array is written,
+ *     the holes of an unpacked matrix and everything around the blocks keep their bits.  No symmetry is applied: of a stored triangle the blocks stored are
+ *     taken from where they lie, the other triangle of the window is not read.  The norms a numeric phase announced are forgotten.
+ *   _from_dense_count  the count half of "a new packed matrix of the tiles of the window that the block filter keeps" (the apply half is
+ *     _from_dense_apply with the index made here): a tile of the block structure row_blk_size [nblkrows] x col_blk_size [nblkcols] (device) is DROPPED iff
+ *     ||tile||_F^2 < eps^2 (filter_count's rule: a NaN norm stays, eps == 0 keeps every tile), norms summed in double in a fixed order.  Writes dst_row_p
+ *     [nblkrows + 1], dst_col_i / dst_blk_p [nblkrows * nblkcols] (device; the first *nblks entries are written: ascending columns inside a row, blk_p the
+ *     running sum of the block sizes) and *nblks, *nze on the host.  Synchronises once.  -1 also for eps < 0 or NaN and for a block structure of more than
+ *     2^31 - 9 tiles; when the sums do not match, nothing of the window has been read. */
+int dbcsr_amd_bcsr_to_dense(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, int kind /* -1, or 0 ... 3: S A H K */, void* dense,
+  int64_t n_rows, int64_t n_cols, int64_t ld, int col_major, void* stream);
+int dbcsr_amd_bcsr_from_dense_apply(void* handle, libsmm_acc_data_t datatype, const void* dense, int64_t n_rows, int64_t n_cols, int64_t ld, int col_major,
+  dbcsr_amd_bcsr* m, void* stream);
+int dbcsr_amd_bcsr_from_dense_count(void* handle, libsmm_acc_data_t datatype, const void* dense, int64_t n_rows, int64_t n_cols, int64_t ld, int col_major,
+  const int32_t* row_blk_size, const int32_t* col_blk_size, int nblkrows, int nblkcols, double eps, int32_t* dst_row_p, int32_t* dst_col_i,
+  int64_t* dst_blk_p, int64_t* nblks, int64_t* nze, void* stream);
 
 /* Measurement helper (bench.py, roofline.fabric): what the L2 <-> Infinity-Cache fabric of the current device delivers, in TB/s -- a
  * plain streaming read of a 160 MB window by all CUs, and the block gather of the block-product dataflow (4232-byte blocks from

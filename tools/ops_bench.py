@@ -65,6 +65,15 @@ any alternation:
 
     python tools/ops_bench.py --block-inverse --alternations 7 --warmup 2 --out profiles/block_inverse.txt
 
+With --dense only the dense conversion is timed (dbcsr_to_dense, dbcsr_from_dense, dbcsr_create_from_dense; kernels of dbcsr_amd/csrc/mm_dense.h) on a
+float64 matrix of 504 x 504 blocks of 23 x 23 (n = 11592: a dense matrix of 1.07 GB), once with every block stored and once with one block in ten,
+alternating: to_dense into a row-by-row and into a column-by-column tensor, from_dense out of both, create_from_dense(eps) (a wall-clock row: it answers on
+the host), and the yardsticks out.copy_(src) and out.copy_(src.T) of a dense tensor of that size (the vendor's straight and transposing copies),
+torch.zeros of that size, and the host round trip the feature replaces (to_host, the block loop of oracle.Bcsr.to_dense, upload, synchronise; wall clock,
+one call per sample) against dbcsr_to_dense timed the same way.  The condition: the device path is faster than the host round trip in every alternation:
+
+    python tools/ops_bench.py --dense --alternations 7 --warmup 2 --out profiles/dense_conversion.txt
+
 A sample is `--reps` calls back to back between two device events, divided by reps.  Bytes are counted from the shapes: 8 * (elements read + elements
 written) of the data areas, index arrays left out.  Spread = (max - min) / median over the samples."""
 import argparse
@@ -81,6 +90,7 @@ from dbcsr_amd import lib as L  # noqa: E402
 from dbcsr_amd.matrix import DbcsrMatrix, StreamHandle  # noqa: E402
 from dbcsr_amd.multiply import MultiplyEngine  # noqa: E402
 from dbcsr_amd.operations import dbcsr_add, dbcsr_get_block_diag, dbcsr_invert_block_diag, dbcsr_scale  # noqa: E402
+from dbcsr_amd.operations import dbcsr_create_from_dense, dbcsr_from_dense, dbcsr_to_dense  # noqa: E402
 
 
 def matrix_of(mask, b, seed):
@@ -407,6 +417,86 @@ def block_inverse(args, say, lines, rng):
             f.write("\n".join(lines) + "\n")
 
 
+def dense_conversion(args, say, lines, rng):
+    from oracle import oracle as O
+    E = MultiplyEngine()
+    b, nb = 23, 504
+    n = b * nb
+    results = {}
+    src = torch.rand((n, n), dtype=torch.float64, device="cuda") - 0.5
+    out_r = torch.empty((n, n), dtype=torch.float64, device="cuda")
+    out_c = torch.empty((n, n), dtype=torch.float64, device="cuda").T
+    for fill in (1.0, 0.1):
+        M = matrix_of(rng.random((nb, nb)) < fill, b, 40)
+        # what is timed is right: against the host helper, bit for bit, on the first block rows (the whole comparison is the tests' business)
+        rs, cs, row_p, col_i, blk_p, data = M.to_host()
+        head = 8
+        H = O.Bcsr(rs[:head], cs, row_p[:head + 1], col_i[:row_p[head]], blk_p[:row_p[head]], data).to_dense()
+        for out in (out_r, out_c):
+            out.fill_(float("nan"))
+            dbcsr_to_dense(M, out=out, engine=E)
+            if out[:head * b].cpu().numpy().tobytes() != H.tobytes() or bool(torch.isnan(out).any()):
+                sys.exit("dbcsr_to_dense is wrong: nothing is timed")
+        del rs, cs, row_p, col_i, blk_p, data, H
+        X = M.copy()
+        eps = 1e-3
+
+        def host_round_trip():
+            rs, cs, row_p, col_i, blk_p, data = M.to_host()
+            D = torch.as_tensor(O.Bcsr(rs, cs, row_p, col_i, blk_p, data).to_dense()).cuda()
+            torch.cuda.synchronize()
+            return D
+
+        run = {
+            "copy": lambda: out_r.copy_(src),
+            "copy.T": lambda: out_r.copy_(src.T),
+            "zeros": lambda: torch.zeros((n, n), dtype=torch.float64, device="cuda"),
+            "to_dense.rows": lambda: dbcsr_to_dense(M, out=out_r, engine=E),
+            "to_dense.cols": lambda: dbcsr_to_dense(M, out=out_c, engine=E),
+            "from_dense.rows": lambda: dbcsr_from_dense(out_r, X, engine=E),
+            "from_dense.cols": lambda: dbcsr_from_dense(out_c, X, engine=E),
+            "create(eps)": lambda: dbcsr_create_from_dense(out_r, M.row_blk_size, M.col_blk_size, eps=eps, engine=E),
+            "device path": lambda: dbcsr_to_dense(M, engine=E),
+            "host path": host_round_trip,
+        }
+        wall = ("create(eps)", "device path", "host path")
+        dbcsr_to_dense(M, out=out_r, engine=E)
+        dbcsr_to_dense(M, out=out_c, engine=E)
+        times = {k: [] for k in run}
+        for step in range(args.warmup + args.alternations):
+            for k in run:
+                x = sample_wall(run[k], 1 if k == "host path" else args.reps) if k in wall else sample(run[k], args.reps)
+                if step >= args.warmup:
+                    times[k].append(x)
+        say("")
+        say("%d x %d blocks of %d x %d, fill %.2f: %d blocks, %.1f MB of blocks, a dense matrix of %.1f MB" % (nb, nb, b, b, fill, M.nblks, 8e-6 * M.nze, 8e-6 * n * n))
+        med = {}
+        for k in run:
+            v = sorted(times[k])
+            med[k] = v[len(v) // 2]
+            moved = {"copy": 2 * n * n, "copy.T": 2 * n * n, "zeros": n * n, "to_dense.rows": n * n + M.nze, "to_dense.cols": n * n + M.nze,
+                     "from_dense.rows": 2 * M.nze, "from_dense.cols": 2 * M.nze}.get(k)
+            say("  %-16s median %9.4f ms  min %9.4f  max %9.4f  spread %5.1f %%  %s   samples: %s"
+                % (k, med[k], v[0], v[-1], 100 * (v[-1] - v[0]) / med[k], "%8.1f GB/s" % (8e-6 * moved / med[k]) if moved else " " * 13,
+                   " ".join("%.4f" % x for x in times[k])))
+        say("  ratios (median / median): to_dense.rows / copy.T %.2f, to_dense.cols / copy %.2f, from_dense.rows / copy.T %.2f, from_dense.cols / copy %.2f, "
+            "to_dense.rows / zeros %.2f" % (med["to_dense.rows"] / med["copy.T"], med["to_dense.cols"] / med["copy"], med["from_dense.rows"] / med["copy.T"],
+                                            med["from_dense.cols"] / med["copy"], med["to_dense.rows"] / med["zeros"]))
+        results[fill] = times
+        del M, X
+    say("")
+    say("condition: the device path (dbcsr_to_dense, allocation included, synchronised) is faster than the host round trip in every alternation")
+    ok = True
+    for fill, times in results.items():
+        r = sorted(x / z for x, z in zip(times["device path"], times["host path"]))
+        ok = ok and r[-1] < 1.0
+        say("  fill %.2f: device path / host path  %.6f ... %.6f   %s" % (fill, r[0], r[-1], "holds" if r[-1] < 1.0 else "FAILS"))
+    say("  the condition %s" % ("holds" if ok else "FAILS"))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=32768)
@@ -421,6 +511,7 @@ def main():
     ap.add_argument("--multivec", action="store_true", help="only the matrix times several dense vectors and its yardsticks")
     ap.add_argument("--rank-update", action="store_true", help="only the rank-k update on the stored pattern and its yardsticks")
     ap.add_argument("--block-inverse", action="store_true", help="only the block diagonal: get_block_diag, invert_block_diag and what they replace")
+    ap.add_argument("--dense", action="store_true", help="only the dense conversion: to_dense, from_dense, create_from_dense and what they replace")
     ap.add_argument("--mfma-tflops", type=float, default=None, help="with --rank-update: the fp64 MFMA figure bench.py --full measured in the same session")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     args = ap.parse_args()
@@ -441,7 +532,9 @@ def main():
         return rank_update(args, say, lines, rng, b, nb, st)
     if args.block_inverse:
         return block_inverse(args, say, lines, rng)
-    only = ("norm", "norm.T", "matvec.N", "matvec.T", "matvec.S", "gersh.N", "colnorm", "gersh.S") if args.matvec else None
+    if args.dense:
+        return dense_conversion(args, say, lines, rng)
+    only =("norm", "norm.T", "matvec.N", "matvec.T", "matvec.S", "gersh.N", "colnorm", "gersh.S") if args.matvec else None
     # the same-pattern pair
     mask = rng.random((nb, nb)) < args.fill_flat
     A, B = matrix_of(mask, b, 1), matrix_of(mask, b, 2)
