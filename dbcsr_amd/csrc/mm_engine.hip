@@ -37,8 +37,8 @@
 //   mm_engine_lab.h      lab build: hosts of the experimental dataflows and their family switch
 //   mm_engine_ops.h      init_c, crop, filter, checksum, fill, transpose, twin moves, statistics
 //   mm_engine_algebra.h  add (count / apply), add_on_diag pieces, trace, dot, norm, norms and vectors, matvec, multivec, rank update (kernels: mm_algebra.h,
-//                        mm_multivec.h, mm_rank_update.h, over the block walk of mm_block_walk.h), the block diagonal (mm_block_inverse.h) and the dense
-//                        conversion (mm_dense.h)
+//                        mm_multivec.h, mm_rank_update.h, over the block walk of mm_block_walk.h), the block diagonal (mm_block_inverse.h), its product with a
+//                        matrix (mm_block_scale.h) and the dense conversion (mm_dense.h)
 // This file: create / destroy, the symbolic phase, and the numeric phase as a sequence -- product lists, choice, set-up, launch, plan bookkeeping.
 #include <hip/hip_runtime.h>
 
@@ -69,6 +69,7 @@
 #include "mm_multivec.h"  // the matrix times several dense vectors
 #include "mm_rank_update.h"  // the rank-k update on the stored pattern
 #include "mm_block_inverse.h"  // the block diagonal: its copy and the batched inverse of its blocks
+#include "mm_block_scale.h"  // a block diagonal applied to a matrix in place
 #include "mm_dense.h"  // dense <-> block-sparse: to_dense, from_dense and the count half of create_from_dense
 // The library comes in two builds (Makefile): the SHIPPING one holds what a multiply can run by itself -- the kernels listed above, their
 // symbolic phases, plan reuse -- and the LAB one (-DDBCSR_AMD_EXPERIMENTS, libdbcsr_acc_amd_lab.so) adds every dataflow and variant that

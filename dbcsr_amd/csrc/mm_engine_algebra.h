@@ -1,8 +1,8 @@
 // mm_engine_algebra.h -- part of mm_engine.hip (included inside extern "C", after mm_engine_ops.h): the C-ABI operations between multiplies --
 // dbcsr_amd_bcsr_add_count / _add_apply, the pieces of dbcsr_add_on_diag (dbcsr_amd_bcsr_diag_count / _diag_fill / _diag_shift), dbcsr_amd_bcsr_trace,
 // _dot, _norm2, and the norms and vectors: dbcsr_amd_bcsr_maxabs, _row_sums, _col_sums, _gershgorin, _get_diag, _set_diag, _scale_by_vector, _matvec, _multivec, _rank_update,
-// the block diagonal: dbcsr_amd_bcsr_block_diag_count / _apply / _invert, and the dense conversion: dbcsr_amd_bcsr_to_dense / _from_dense_apply /
-// _from_dense_count.  Kernels: mm_algebra.h, mm_multivec.h, mm_rank_update.h, mm_block_inverse.h, mm_dense.h. The reductions, the diagonal pieces, the same-pattern add and the norms and vectors use buffers of their own (Engine::alg_*) and the
+// the block diagonal: dbcsr_amd_bcsr_block_diag_count / _apply / _invert / _multiply, and the dense conversion: dbcsr_amd_bcsr_to_dense / _from_dense_apply /
+// _from_dense_count.  Kernels: mm_algebra.h, mm_multivec.h, mm_rank_update.h, mm_block_inverse.h, mm_block_scale.h, mm_dense.h. The reductions, the diagonal pieces, the same-pattern add and the norms and vectors use buffers of their own (Engine::alg_*) and the
 // scan's scratch, which no saved plan depends on (the checksum uses it the same way): they do NOT invalidate the plan.  The union add borrows the
 // symbolic phase's bitmaps and prefix arrays and invalidates it, as filter and crop do.
 #ifndef DBCSR_AMD_MM_ENGINE_ALGEBRA_H
@@ -825,6 +825,51 @@ int dbcsr_amd_bcsr_block_diag_invert(void* handle, libsmm_acc_data_t datatype, d
     info[2] = E->host_scalars[2];
   }
   return check(hipGetLastError(), "dbcsr_amd_bcsr_block_diag_invert", __FILE__, __LINE__);
+}
+// ---- block diagonal times matrix (kernels: mm_block_scale.h) -------------------------------------------------------------------------------------------------
+extern "C++" {
+// waves per block row: about one stored block per wave (a block is ceil(len / 16) strips of up to six MFMA tiles each -- work enough for a wave)
+static inline int block_scale_split(int64_t nbr, int64_t nblks) {
+  if (nbr <= 0) return 1;
+  return (int)std::max<int64_t>(1, std::min<int64_t>((nblks + nbr - 1) / nbr, 1024));
+}
+
+template <typename T>
+static void block_scale_launch(hipStream_t st, const dbcsr_amd_bcsr* diag, dbcsr_amd_bcsr* m, int left, int tr, int conj, bool zero, const double alpha[2]) {
+  using Acc = typename MatvecAcc<T>::type;
+  const int nbr = m->nblkrows, S = block_scale_split(nbr, m->nblks);
+  const dim3 grid = grid_for((int64_t)nbr * S * 64);
+  if (zero)
+    hipLaunchKernelGGL((block_scale_zero<T>), grid, dim3(256), 0, st, m->row_p, m->col_i, m->blk_p, static_cast<T*>(m->data), m->row_blk_size,
+                       m->col_blk_size, nbr, S);
+  else if (left)
+    hipLaunchKernelGGL((block_scale_left<T>), grid, dim3(256), 0, st, m->row_p, m->col_i, m->blk_p, static_cast<T*>(m->data), m->row_blk_size,
+                       m->col_blk_size, diag->row_p, diag->col_i, diag->blk_p, static_cast<const T*>(diag->data), nbr, S, tr, conj,
+                       algebra_scalar<Acc>(alpha));
+  else
+    hipLaunchKernelGGL((block_scale_right<T>), grid, dim3(256), 0, st, m->row_p, m->col_i, m->blk_p, static_cast<T*>(m->data), m->row_blk_size,
+                       m->col_blk_size, diag->row_p, diag->col_i, diag->blk_p, static_cast<const T*>(diag->data), nbr, S, tr, conj,
+                       algebra_scalar<Acc>(alpha));
+}
+}  // extern "C++"
+
+int dbcsr_amd_bcsr_block_diag_multiply(void* handle, libsmm_acc_data_t datatype, char side, char trans, const double alpha[2], const dbcsr_amd_bcsr* diag,
+                                       dbcsr_amd_bcsr* m, int max_dim, void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E || !alpha || !diag || !m || max_dim < 0 || diag->nblkrows != diag->nblkcols) return -1;
+  if (side != 'L' && side != 'R') return -1;
+  if (trans != 'N' && trans != 'T' && trans != 'C' && trans != 'J') return -1;
+  if (diag->nblkrows != (side == 'L' ? m->nblkrows : m->nblkcols)) return -1;
+  if (!algebra_type(datatype)) return -10;
+  if (max_dim > kBlockScaleMaxDim) return -11;
+  if (m->nblks > 0 && diag->nblks > 0 && diag->data == m->data) return -1;   // (in place on m: the operand is another data area)
+  engine_writes_values(E);
+  hipStream_t st = stream_of(stream);
+  if (m->nblkrows == 0 || m->nblkcols == 0 || m->nblks == 0) return 0;   // an empty matrix: nothing to write
+  const bool zc = datatype == dbcsr_type_complex_8;
+  const int tr = trans == 'T' || trans == 'C' ? 1 : 0, conj = zc && (trans == 'C' || trans == 'J') ? 1 : 0;
+  DBCSR_AMD_BY_TYPE(block_scale_launch, st, diag, m, side == 'L' ? 1 : 0, tr, conj, algebra_is_zero(datatype, alpha), alpha);
+  return check(hipGetLastError(), "dbcsr_amd_bcsr_block_diag_multiply", __FILE__, __LINE__);
 }
 // ---- dense conversion (kernels: mm_dense.h) -----------------------------------------------------------------------------------------------------------------
 // Everything here works in Engine::alg_i32 / alg_i64 and the scan's scratch: no entry invalidates the plan or writes a work area of the symbolic phase.

@@ -48,6 +48,8 @@ MM_SYMBOLS = [
     "dbcsr_amd_bcsr_rank_update",
     # block diagonal
     "dbcsr_amd_bcsr_block_diag_count", "dbcsr_amd_bcsr_block_diag_apply", "dbcsr_amd_bcsr_block_diag_invert",
+    # block diagonal times matrix
+    "dbcsr_amd_bcsr_block_diag_multiply",
     # dense conversion
     "dbcsr_amd_bcsr_to_dense", "dbcsr_amd_bcsr_from_dense_apply", "dbcsr_amd_bcsr_from_dense_count",
 ]
@@ -216,6 +218,7 @@ def load_library(lab=False):
     L.dbcsr_amd_bcsr_block_diag_count.argtypes = [vp, BP, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32), vp]
     L.dbcsr_amd_bcsr_block_diag_apply.argtypes = [vp, i32, BP, BP, vp]
     L.dbcsr_amd_bcsr_block_diag_invert.argtypes = [vp, i32, BP, i32, C.POINTER(i64), vp]
+    L.dbcsr_amd_bcsr_block_diag_multiply.argtypes = [vp, i32, C.c_char, C.c_char, Z, BP, BP, i32, vp]
     L.dbcsr_amd_bcsr_to_dense.argtypes = [vp, i32, BP, i32, vp, i64, i64, i64, i32, vp]
     L.dbcsr_amd_bcsr_from_dense_apply.argtypes = [vp, i32, vp, i64, i64, i64, i32, BP, vp]
     L.dbcsr_amd_bcsr_from_dense_count.argtypes = [vp, i32, vp, i64, i64, i64, i32, vp, vp, i32, i32, C.c_double, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), vp]

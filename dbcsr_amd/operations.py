@@ -17,6 +17,7 @@
     dbcsr_rank_update(matrix, vecs_x, vecs_y, alpha, beta, trans)  A_IJ <- beta*A_IJ + alpha*X_I*op(Y_J) on the stored blocks only (not a mirror, see there)
     dbcsr_get_block_diag(matrix)                                a new matrix of the diagonal blocks the matrix stores
     dbcsr_invert_block_diag(matrix, check)                      every stored diagonal block <- its inverse, in place (not a mirror, see there)
+    dbcsr_scale_by_block_diag(matrix, diag, side, trans, alpha) A_IJ <- alpha*op(D_I)*A_IJ ("left"), alpha*A_IJ*op(D_J) ("right") or both, in place (not a mirror)
     dbcsr_to_dense(matrix, out)                                 the full matrix as a dense device tensor (dbcsr_to_dense_local / copy_dbcsr_to_fm)
     dbcsr_from_dense(dense, matrix)                             the stored blocks <- the dense tensor's elements (copy_fm_to_dbcsr, keep_sparsity)
     dbcsr_create_from_dense(dense, row_blk_size, col_blk_size, eps)  a new matrix of the blocks of a dense tensor that the block filter keeps
@@ -609,6 +610,94 @@ def dbcsr_invert_block_diag(matrix, check=True, engine=None, stream=None):
     if rc != 0:
         raise RuntimeError("dbcsr_amd_bcsr_block_diag_invert failed (%d)" % rc)
     return (int(info[0]), int(info[1])) if check else None
+
+
+def _data_overlap(a, b):
+    """the data areas of two matrices intersect (the same tensor, or two views of one allocation)"""
+    if not a.numel() or not b.numel():
+        return False
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def _same_blk_sizes(a, b):
+    return a is b or (a.numel() == b.numel() and torch.equal(a, b))
+
+
+_BLOCK_SCALE_DAGGER = {"N": "C", "C": "N", "T": "J"}   # op' = op followed by the conjugate transpose ('J': the conjugate alone)
+
+
+def dbcsr_scale_by_block_diag(matrix, diag, side, trans="N", alpha=1.0, engine=None, stream=None):
+    """The block analogue of dbcsr_scale_by_vector: every stored block of `matrix` is multiplied by a diagonal block of `diag`, in place, and nothing else.
+        side="left":   A_IJ <- alpha * op(D_I) * A_IJ                 (the block-Jacobi preconditioned operator D^-1 A, the first Newton-Schulz product X0 S)
+        side="right":  A_IJ <- alpha * A_IJ * op(D_J)
+        side="both":   A_IJ <- alpha * op(D_I) * A_IJ * op(D_J)^+     (a block congruence; ^+ the transpose, for complex data the conjugate transpose)
+    NOT a mirror of a routine of the reference: there the product goes through dbcsr_multiply, with a symbolic phase, a second matrix and a new index for
+    the result.  Here the product has the pattern of the matrix itself.  op is "N", "T" or "C" (conjugate transpose; real data: "T").  D_I is the diagonal
+    block (I, I) that diag STORES: blocks of diag off the diagonal are never read -- the operand is blockdiag(diag).  A block row of diag without a stored
+    diagonal block counts as a zero block, as it would in dbcsr_multiply(diag, A, beta=0, retain_sparsity): the blocks of the matrix in that block row
+    (left) or block column (right) become +0.0 and their old values are not read, so a NaN there does not survive.  alpha == 0: every element of every
+    stored block becomes +0.0 and neither operand's data is read.  side="both" is the left pass (with alpha) followed by the right pass with op followed
+    by ^+, on the same stream: two launches, two roundings per element.
+    Products and sums in double / complex double (float32 converted on load), alpha applied in double, one rounding to the data's type per element and
+    pass; no atomics, the same bits on every call.  No index array is written: index_stamp() of both matrices stays and a multiply that had the matrix as
+    operand before reuses its plan; the holes of an unpacked matrix and the bytes around the data area keep their bits.
+    Matrix symmetry 'N': any side.  'S' (real data) and 'H': side="both" only, which keeps the symmetry ('H': real alpha) -- the stored triangle is
+    transformed block by block, which is the congruence of the full matrix.  'A', 'K' and 'S' of complex data: ValueError (not yet).  diag 'N', 'S', 'H':
+    its stored full diagonal blocks are taken as they are, as in dbcsr_invert_block_diag; 'A' / 'K': ValueError.  diag must have a square block structure
+    whose block sizes are the matrix' row block sizes (left, both) and column block sizes (right, both), the matrix' data type (TypeError), and a data
+    area that does not overlap the matrix' (ValueError; diag is matrix included).  A diagonal block dimension above 96: NotImplementedError (what can be
+    inverted can be applied); the other dimension of a block of the matrix is not limited.  Every refusal comes before any call of the library.
+    Asynchronous on the stream; returns None."""
+    name = "dbcsr_scale_by_block_diag"
+    if side not in ("left", "right", "both"):
+        raise ValueError("%s: side must be 'left', 'right' or 'both', got %r" % (name, side))
+    if trans not in ("N", "T", "C"):
+        raise ValueError("%s: trans must be 'N', 'T' or 'C', got %r" % (name, trans))
+    sym, dsym = _check_symmetry(name, matrix), _check_symmetry(name, diag)
+    if matrix.dtype != diag.dtype:
+        raise TypeError("%s: data types of the matrix and of diag differ" % name)
+    matrix.dtype_code
+    zc = matrix.dtype.is_complex
+    if not zc and trans == "C":
+        trans = "T"   # (real data: the conjugate transpose is the transpose)
+    _check_scalar(name, matrix, alpha)
+    if dsym in ("A", "K"):
+        raise ValueError("%s: diag with symmetry %r (its diagonal blocks are not stored as they are)" % (name, dsym))
+    if sym in ("A", "K") or (sym == "S" and zc):
+        raise ValueError("%s: not yet for a matrix with symmetry %r%s" % (name, sym, " of complex data" if sym == "S" else ""))
+    if sym != "N":
+        matrix.symmetry_kind()   # (which symmetries go with which data)
+        _check_square(name, matrix)
+        if side != "both":
+            raise ValueError("%s: a matrix with symmetry %r takes side='both' (one side alone does not keep the symmetry)" % (name, sym))
+        if sym == "H" and complex(alpha).imag != 0:
+            raise ValueError("%s: a hermitian matrix takes a real alpha" % name)
+    if diag.nblkrows != diag.nblkcols or not _same_blk_sizes(diag.row_blk_size, diag.col_blk_size):
+        raise ValueError("%s: diag is not square in its block structure" % name)
+    if side in ("left", "both") and not _same_blk_sizes(diag.row_blk_size, matrix.row_blk_size):
+        raise ValueError("%s: the block sizes of diag differ from the matrix' row block sizes" % name)
+    if side in ("right", "both") and not _same_blk_sizes(diag.row_blk_size, matrix.col_blk_size):
+        raise ValueError("%s: the block sizes of diag differ from the matrix' column block sizes" % name)
+    if diag is matrix or _data_overlap(diag.data, matrix.data):
+        raise ValueError("%s: diag.data overlaps matrix.data (the update is in place)" % name)
+    max_dim = _max_size(diag.row_blk_size)
+    if max_dim > BLOCK_INVERSE_MAX_DIM:
+        raise NotImplementedError("%s: a diagonal block of %d (diagonal blocks of up to %d are applied)" % (name, max_dim, BLOCK_INVERSE_MAX_DIM))
+    E = engine or default_engine()
+    st = StreamHandle(stream)
+    d, a = diag.desc(), matrix.desc()   # (only the matrix' data area is written)
+    if alpha == 0:
+        passes = (("R" if side == "right" else "L", trans, 0.0),)   # (zeros without a read: one launch, whatever the side)
+    elif side == "both":
+        dagger = _BLOCK_SCALE_DAGGER[trans] if zc else ("T" if trans == "N" else "N")
+        passes = (("L", trans, alpha), ("R", dagger, 1.0))
+    else:
+        passes = (("L" if side == "left" else "R", trans, alpha),)
+    for sd, op, al in passes:
+        rc = E.L.dbcsr_amd_bcsr_block_diag_multiply(E.h, matrix.dtype_code, sd.encode(), op.encode(), _z(al), C.byref(d), C.byref(a), max_dim, st.ptr)
+        if rc != 0:
+            raise RuntimeError("dbcsr_amd_bcsr_block_diag_multiply failed (%d)" % rc)
 
 
 # ---- dense conversion ------------------------------------------------------------------------------------------------------------------------------

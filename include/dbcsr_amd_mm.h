@@ -463,6 +463,26 @@ int dbcsr_amd_bcsr_block_diag_count(void* handle, const dbcsr_amd_bcsr* m, int32
 int dbcsr_amd_bcsr_block_diag_apply(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, dbcsr_amd_bcsr* dst, void* stream);
 int dbcsr_amd_bcsr_block_diag_invert(void* handle, libsmm_acc_data_t datatype, dbcsr_amd_bcsr* m, int max_dim, int64_t info[3], void* stream);
 
+/* Block diagonal times matrix: the block analogue of _scale_by_vector, in place on every block the index of m names and on nothing else -- D^-1 A of a
+ * block-Jacobi preconditioner, X0 S of a Hotelling / Newton-Schulz inverse, and as two calls a block congruence D A D^T -- without a symbolic phase, a
+ * plan or a second matrix: the product has the pattern of m itself.
+ *   _block_diag_multiply  side 'L': A_IJ <- alpha op(D_I) A_IJ; side 'R': A_IJ <- alpha A_IJ op(D_J); D_I the diagonal block (I, I) that diag stores.
+ *     Blocks of diag off the diagonal are never read: the operand is blockdiag(diag).  A block row of diag without a stored diagonal block counts as a zero
+ *     block: the blocks of m in that block row (L) or block column (R) become +0.0 and their old values are not read.  op: trans 'N', 'T' (transpose),
+ *     'C' (conjugate transpose; real data: 'T') or 'J' (the conjugate, not transposed; real data: 'N' -- the second pass of a congruence with op = T).
+ *     diag has a square block structure whose block sizes are m's row block sizes (L) or column block sizes (R): the caller's contract, as is that the
+ *     two data areas do not overlap (-1 when they start at the same address).  max_dim is the caller's bound on the dimension of a diagonal block; the
+ *     other dimension of a block of m is not limited.  Products and sums in double / complex double (real_4 converted on load), alpha applied in double,
+ *     one rounding to the data's type per element; a strip of 16 element columns (L) or rows (R) of a block is read completely before any of it is
+ *     stored and has one owner: no atomics, the same bits on every call.  alpha == 0: every element of every stored block becomes +0.0 and neither
+ *     operand's data is read.  No index array is written; the holes of an unpacked matrix and everything around the blocks keep their bits; buffers
+ *     of the symbolic phase are not touched, a saved plan stays.  Asynchronous on stream, no synchronisation.  -1 for a null handle, scalar or matrix,
+ *     a bad side or trans, max_dim < 0, diag->nblkrows != diag->nblkcols or != m's block rows (L) / block columns (R); -10 for a data type the algebra
+ *     does not know; -11 for max_dim above 96 (what _block_diag_invert can invert can be applied), with nothing launched; 0 with nothing written for
+ *     an empty matrix. */
+int dbcsr_amd_bcsr_block_diag_multiply(void* handle, libsmm_acc_data_t datatype, char side /* 'L' 'R' */, char trans, const double alpha[2],
+  const dbcsr_amd_bcsr* diag, dbcsr_amd_bcsr* m, int max_dim, void* stream);
+
 /* Dense conversion: dbcsr_to_dense_local of the reference and CP2K's copy_dbcsr_to_fm / copy_fm_to_dbcsr(keep_sparsity), between a matrix and a dense
  * device tensor, without leaving the device.  `dense` is the window [n_rows, n_cols] of elements of the data type, element (i, j) at i * ld + j
  * (col_major 0: row by row, as a torch tensor or a column slice of a wider one; ld >= n_cols) or at i + j * ld (col_major != 0: column by column, as a

@@ -55,6 +55,13 @@ in every alternation:
 
     python tools/ops_bench.py --rank-update --alternations 7 --warmup 2 --mfma-tflops T --out profiles/rank_update.txt
 
+With --block-scale only the block diagonal applied to a matrix is timed (dbcsr_scale_by_block_diag; kernels of dbcsr_amd/csrc/mm_block_scale.h) on the
+standard matrix (--n / --block, full as config 2's product is) and on blocks of 32: the left, right and both passes against dbcsr_scale of the same matrix
+(the floor: A read and written once) and against what replaces it without the kernel, dbcsr_multiply(D, A -> C) with a warm plan and with a cold one
+(DBCSR_AMD_MM_PLAN=0), all alternating in one process; 2 nze b / time against --mfma-tflops.
+
+    python tools/ops_bench.py --block-scale --alternations 7 --warmup 2 --mfma-tflops T --out profiles/block_scale.txt
+
 With --block-inverse only the block diagonal is timed (dbcsr_get_block_diag, dbcsr_invert_block_diag; kernels of dbcsr_amd/csrc/mm_block_inverse.h) on
 1424 diagonal blocks of 23 x 23 (the diagonal of config 2's product shape), 32, 64 and 96, float64, alternating: get_block_diag of a matrix with eight more
 blocks per block row, invert_block_diag without and with the check, dbcsr_scale of the block diagonal as the fixed cost of one launch, the device path
@@ -88,8 +95,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from dbcsr_amd import lib as L  # noqa: E402
 from dbcsr_amd.matrix import DbcsrMatrix, StreamHandle  # noqa: E402
-from dbcsr_amd.multiply import MultiplyEngine  # noqa: E402
-from dbcsr_amd.operations import dbcsr_add, dbcsr_get_block_diag, dbcsr_invert_block_diag, dbcsr_scale  # noqa: E402
+from dbcsr_amd.multiply import MultiplyEngine, dbcsr_multiply  # noqa: E402
+from dbcsr_amd.operations import dbcsr_add, dbcsr_get_block_diag, dbcsr_invert_block_diag, dbcsr_scale, dbcsr_scale_by_block_diag  # noqa: E402
 from dbcsr_amd.operations import dbcsr_create_from_dense, dbcsr_from_dense, dbcsr_to_dense  # noqa: E402
 
 
@@ -417,6 +424,75 @@ def block_inverse(args, say, lines, rng):
             f.write("\n".join(lines) + "\n")
 
 
+def block_scale(args, say, lines, rng):
+    E = MultiplyEngine()
+    plan_env = os.environ.get("DBCSR_AMD_MM_PLAN")
+    os.environ["DBCSR_AMD_MM_PLAN"] = "0"
+    E_cold = MultiplyEngine()
+    if plan_env is None:
+        os.environ.pop("DBCSR_AMD_MM_PLAN", None)
+    else:
+        os.environ["DBCSR_AMD_MM_PLAN"] = plan_env
+    results = {}
+    for b in (args.block, 32):
+        nb = args.n // b
+        A = matrix_of(rng.random((nb, nb)) < args.fill_flat, b, 1)
+        # D: I + uniform(-0.5, 0.5) / (10 b) per diagonal block -- a norm near one, so that applying it again and again stays where it is
+        D = matrix_of(np.eye(nb, dtype=bool), b, 50 + b)
+        D.data.mul_(0.1 / b)
+        D.data.view(nb, b, b).add_(torch.eye(b, dtype=torch.float64, device="cuda"))
+        Cm = matrix_of(np.zeros((nb, nb), bool), b, 3)
+        # what is timed is right: the blocks of the first block row against torch (a column-major block read row by row is its transpose)
+        head = int(A.row_p[1].item())
+        before = A.data[:head * b * b].view(head, b, b).clone()
+        dbcsr_scale_by_block_diag(A, D, "left", engine=E)
+        want = before @ D.data[:b * b].view(b, b)
+        err = float(((A.data[:head * b * b].view(head, b, b) - want).abs().max() / want.abs().max()).item())
+        say("%d x %d blocks of %d x %d: left pass on the first block row against torch: max difference / max element = %.2e" % (nb, nb, b, b, err))
+        if not err < 1e-13:
+            sys.exit("the block scaling is wrong: nothing is timed")
+        run = {
+            "scale": lambda: dbcsr_scale(A, 0.9999, engine=E),
+            "left": lambda: dbcsr_scale_by_block_diag(A, D, "left", engine=E),
+            "right": lambda: dbcsr_scale_by_block_diag(A, D, "right", engine=E),
+            "both": lambda: dbcsr_scale_by_block_diag(A, D, "both", engine=E),
+            "multiply.warm": lambda: dbcsr_multiply("N", "N", 1.0, D, A, 0.0, Cm, engine=E),
+            "multiply.cold": lambda: dbcsr_multiply("N", "N", 1.0, D, A, 0.0, Cm, engine=E_cold),
+        }
+        run["multiply.warm"]()
+        torch.cuda.synchronize()
+        times = {k: [] for k in run}
+        for step in range(args.warmup + args.alternations):
+            for k in run:
+                x = sample(run[k], args.reps)
+                if step >= args.warmup:
+                    times[k].append(x)
+        say("")
+        say("A: %d blocks of %d x %d, %.1f MB; D: %d blocks" % (A.nblks, b, b, 8e-6 * A.nze, D.nblks))
+        med = {}
+        for k in run:
+            v = sorted(times[k])
+            med[k] = v[len(v) // 2]
+            say("  %-14s median %9.4f ms  min %9.4f  max %9.4f  spread %5.1f %%  %8.1f GB/s of A   samples: %s"
+                % (k, med[k], v[0], v[-1], 100 * (v[-1] - v[0]) / med[k], 1e-6 * 16 * A.nze / med[k], " ".join("%.4f" % x for x in times[k])))
+        say("")
+        say("time against dbcsr_scale and against the warm multiply (median / median; per alternation, sample by sample), and 2 nze b / time per pass"
+            + (" against %.1f TFLOP/s" % args.mfma_tflops if args.mfma_tflops else ""))
+        for k in ("left", "right", "both"):
+            r = sorted(x / z for x, z in zip(times[k], times["scale"]))
+            q = sorted(x / z for x, z in zip(times[k], times["multiply.warm"]))
+            tf = 2e-9 * A.nze * b * (2 if k == "both" else 1) / med[k]
+            say("  %-6s / scale %6.2f (%.2f ... %.2f)   / multiply.warm %6.3f (%.3f ... %.3f)   / multiply.cold %6.3f   %7.2f TFLOP/s%s"
+                % (k, med[k] / med["scale"], r[0], r[-1], med[k] / med["multiply.warm"], q[0], q[-1], med[k] / med["multiply.cold"], tf,
+                   "   %.3f of the measured MFMA figure" % (tf / args.mfma_tflops) if args.mfma_tflops else ""))
+        results[b] = med
+        del A, D, Cm, before, want
+        torch.cuda.empty_cache()
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def dense_conversion(args, say, lines, rng):
     from oracle import oracle as O
     E = MultiplyEngine()
@@ -511,8 +587,9 @@ def main():
     ap.add_argument("--multivec", action="store_true", help="only the matrix times several dense vectors and its yardsticks")
     ap.add_argument("--rank-update", action="store_true", help="only the rank-k update on the stored pattern and its yardsticks")
     ap.add_argument("--block-inverse", action="store_true", help="only the block diagonal: get_block_diag, invert_block_diag and what they replace")
+    ap.add_argument("--block-scale", action="store_true", help="only the block diagonal applied to a matrix: left, right, both, dbcsr_scale and the multiply it replaces")
     ap.add_argument("--dense", action="store_true", help="only the dense conversion: to_dense, from_dense, create_from_dense and what they replace")
-    ap.add_argument("--mfma-tflops", type=float, default=None, help="with --rank-update: the fp64 MFMA figure bench.py --full measured in the same session")
+    ap.add_argument("--mfma-tflops", type=float, default=None, help="with --rank-update / --block-scale: the fp64 MFMA figure bench.py --full measured in the same session")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "ops_bench.py measures on the GPU"
@@ -532,6 +609,8 @@ def main():
         return rank_update(args, say, lines, rng, b, nb, st)
     if args.block_inverse:
         return block_inverse(args, say, lines, rng)
+    if args.block_scale:
+        return block_scale(args, say, lines, rng)
     if args.dense:
         return dense_conversion(args, say, lines, rng)
     only =("norm", "norm.T", "matvec.N", "matvec.T", "matvec.S", "gersh.N", "colnorm", "gersh.S") if args.matvec else None
