@@ -11,45 +11,15 @@ import torch
 from dbcsr_amd import lib as L
 from dbcsr_amd.multiply import MultiplyEngine
 from oracle import oracle as O
-from tests.gpu_util import to_dev
+from tests.gpu_util import fetch, native_multiply_any, to_dev  # noqa: F401  (fetch: tests/test_gpu_ref_dump.py takes it from here)
 from tests.test_oracle_limits import CASES, limit_case_matrices
 
 pytestmark = pytest.mark.gpu
 
 
-def fetch(lib, ptr, count, dtype):
-    out = np.empty(count, dtype)
-    if count:
-        assert lib.c_dbcsr_acc_memcpy_d2h(C.c_void_p(ptr), out.ctypes.data_as(C.c_void_p), C.c_size_t(out.nbytes), None) == 0
-        assert lib.c_dbcsr_acc_device_synchronize() == 0
-    return out
-
-
 def native_multiply(transa, transb, alpha, A, B, beta, Cm, limits=None, retain=False, eps=0.0, dtype=np.float64):
-    E = MultiplyEngine()
-    lib = E.L
     cast = lambda M: O.Bcsr(M.row_sizes, M.col_sizes, M.row_p, M.col_i, M.blk_p, M.data.astype(dtype))
-    dA, dB, dC = to_dev(cast(A)), to_dev(cast(B)), to_dev(cast(Cm))
-    a, b, c = dA.desc(), dB.desc(), dC.desc()
-    out = L.BcsrDesc()
-    flop = C.c_int64(0)
-    lim = (C.c_int64 * 6)(*limits) if limits is not None else None
-    code = L.dbcsr_type_real_8 if dtype == np.float64 else L.dbcsr_type_real_4
-    rc = lib.dbcsr_amd_multiply(E.h, transa.encode(), transb.encode(), code, float(alpha), C.byref(a), C.byref(b), float(beta), C.byref(c),
-                                lim, 1 if retain else 0, float(eps), C.byref(out), C.byref(flop), None)
-    assert rc == 0
-    torch.cuda.synchronize()
-    nbr = out.nblkrows
-    row_p = fetch(lib, out.row_p, nbr + 1, np.int32)
-    nblks = int(out.nblks)
-    assert row_p[-1] == nblks
-    col_i = fetch(lib, out.col_i, nblks, np.int32)
-    blk_p = fetch(lib, out.blk_p, nblks, np.int64)
-    rows = np.repeat(np.arange(nbr), np.diff(row_p))
-    nze = int((Cm.row_sizes[rows].astype(np.int64) * Cm.col_sizes[col_i]).sum()) if nblks else 0
-    data = fetch(lib, out.data, nze, dtype)
-    assert lib.dbcsr_amd_bcsr_release(C.byref(out)) == 0
-    return O.Bcsr(Cm.row_sizes, Cm.col_sizes, row_p, col_i, blk_p, data), flop.value
+    return native_multiply_any(MultiplyEngine(), transa, transb, alpha, cast(A), cast(B), beta, cast(Cm), limits=limits, retain=retain, eps=eps)
 
 
 def same(got, ref, tol):

@@ -2,7 +2,8 @@
 transposes, alpha / beta (including 0 and 1), retain_sparsity, filter_eps and product-matrix symmetry through the dbcsr_multiply mirror
 against the CPU oracle -- index bit-exact, flop identical, values 1e-10 (fp64) / 2e-5 (fp32).  The hand-picked cases of the other
 files pin known corners; this one walks the combinations nobody thought of (empty rows, C blocks without products, single-block
-matrices, lists longer and shorter than the kernels' windows) through whatever kernel the engine picks."""
+matrices, lists longer and shorter than the kernels' windows) through whatever kernel the engine picks.  The first 40 cases also run through the C
+entry (test_random_multiply_native_entry); the axes this sweep does not draw are those of tests/test_gpu_option_sweep.py."""
 import os
 
 import numpy as np
@@ -11,7 +12,7 @@ import torch
 
 from dbcsr_amd.multiply import MultiplyEngine, dbcsr_multiply
 from oracle import oracle as O
-from tests.gpu_util import dev_to_bcsr, to_dev
+from tests.gpu_util import dev_to_bcsr, native_multiply_any, to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -149,5 +150,17 @@ def compare_case(c, out, flop, ref, info):
 def run_case(c):
     A, B, Cm, ref, info = build_case(c)
     out, flop = device_case(c, A, B, Cm)
+    bad = compare_case(c, out, flop, ref, info)
+    assert bad is None, (bad, c)
+
+
+@pytest.mark.parametrize("seed", range(40))
+def test_random_multiply_native_entry(seed):
+    """the first 40 cases of test_random_multiply_matches_oracle through the other orchestration, the C entry a Fortran host calls (dbcsr_amd_multiply,
+    dbcsr_amd_multiply_symmetric_c for a product with symmetry), held to the same comparison"""
+    c = make_case(1000 + seed)
+    A, B, Cm, ref, info = build_case(c)
+    out, flop = native_multiply_any(MultiplyEngine(), c["ta"], c["tb"], c["alpha"], A, B, c["beta"], Cm, retain=c["retain"], eps=c["eps"],
+                                    symm_c=c["symm_c"])
     bad = compare_case(c, out, flop, ref, info)
     assert bad is None, (bad, c)
