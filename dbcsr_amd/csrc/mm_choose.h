@@ -380,5 +380,53 @@ static inline NumericChoice choose_numeric(const SizeFacts& f, const Switches& s
   return pick(Family::f64_lds, lds_grid, dbg_flags, "mm_numeric_f64_lds<%d>", c.maxt);
 }
 
+// ---- the symbolic phase's choices ------------------------------------------------------------------------------------------------------------------------------
+// Which kernels build C's pattern, count and list the block products, and how C is cut into column panels: pure functions of the block counts, the forced
+// mode and the panel size (tests/test_symbolic_scale_cpu.py).  The number of C blocks is known only after the pattern kernels ran, so the choice comes in
+// two steps: choose_symbolic_pattern before, choose_symbolic_count after.  dbcsr_amd_mm_last_symbolic reports what they chose.
+struct SymbolicSizes {
+  int nbr = 0, nbk = 0, nbc = 0;        // block rows of A / C, inner blocks, block columns of B / C
+  int64_t a_nblks = 0, b_nblks = 0;
+  bool filtering = false, retain = false;
+  int forced = 0;                       // DBCSR_AMD_MM_SYMBOLIC: 0 automatic, 1 word, 2 grid, 3 rows
+};
+
+struct SymbolicChoice {
+  bool sparse_guess = false;            // fewer products expected than 60 % of the (row, column) candidates, enough block rows to fill the chip
+  bool bitmap_rows = false;             // C's pattern under the on-the-fly filter by the product-driven kernel (c_bitmap_rows_filtered)
+  bool grid_kernels = false, rows_kernels = false;   // count / fill: one lane per candidate, one wave per block row (neither: one thread per bitmap word)
+};
+
+// before C's pattern: expected number of products against the number of (row, column) candidates
+static inline SymbolicChoice choose_symbolic_pattern(const SymbolicSizes& s) {
+  SymbolicChoice c;
+  const double prod_est = (double)s.a_nblks * ((double)s.b_nblks / (double)std::max(s.nbk, 1));
+  c.sparse_guess = s.forced == 3 || (s.forced == 0 && s.nbr >= 2048 && prod_est < 0.6 * (double)s.nbr * (double)s.nbc);
+  c.bitmap_rows = s.filtering && c.sparse_guess && !s.retain;
+  return c;
+}
+
+// after C's pattern: one lane per (row, column) candidate unless C is extremely sparse (then one thread per bitmap word); a sparse C (less than 60 % of the
+// candidates are blocks) with enough block rows to fill the chip: the product-driven kernels
+static inline SymbolicChoice choose_symbolic_count(const SymbolicSizes& s, SymbolicChoice c, int64_t c_nblks) {
+  const int nJ = (s.nbc + 63) / 64;
+  c.grid_kernels = s.filtering || (((int64_t)s.nbr * nJ * 64 <= 256 * std::max<int64_t>(c_nblks, 1)) && s.forced != 1);
+  c.rows_kernels = s.forced == 3 || (s.forced == 0 && s.nbr >= 2048 && 10 * c_nblks < 6 * (int64_t)s.nbr * s.nbc);
+  if (c.rows_kernels) c.grid_kernels = false;
+  return c;
+}
+
+// column panels of C sized so that B's panel stays in the Infinity Cache: NP panels of PW bitmap words (the last one may be narrower; W % PW need not be 0)
+static inline void choose_panels(int W, int64_t b_bytes_est, int64_t panel_bytes, int* NP_out, int* PW_out) {
+  int NP = (int)std::min<int64_t>((b_bytes_est + panel_bytes - 1) / panel_bytes, (int64_t)W);
+  if (NP < 1) NP = 1;
+  const int PW = (W + NP - 1) / NP;
+  *NP_out = (W + PW - 1) / PW;
+  *PW_out = PW;
+}
+
+// DBCSR_AMD_MM_PANEL_MB / DBCSR_AMD_MM_GROUP_PANEL_MB in bytes: at least 1 MB (choose_panels divides by it)
+static inline int64_t panel_bytes_of_mb(long long mb) { return (int64_t)std::max<long long>(mb, 1) << 20; }
+
 }  // namespace dbcsr_amd
 #endif

@@ -390,6 +390,10 @@ int dbcsr_amd_mm_symbolic_filtered(void* handle, libsmm_acc_data_t datatype, dou
     counts->c_nblks = counts->c_nze = counts->nproducts = counts->flop = 0;
     E->facts.c_nblks = 0;
     E->facts.nproducts = 0;
+    E->grid_kernels = E->rows_kernels = false;
+    E->facts.cls_mode = false;
+    E->sym_bitmap = -1;
+    E->sym_NP = E->sym_PW = E->sym_rowp_chunks = 0;
     E->valid = true;
     return 0;
   }
@@ -430,9 +434,11 @@ int dbcsr_amd_mm_symbolic_filtered(void* handle, libsmm_acc_data_t datatype, dou
   }
   // 2. pattern of C_out, its row prefix and row pointer
   // expected number of products against the number of (row, column) candidates: product-driven kernels for a sparse product
-  const double prod_est = (double)a->nblks * ((double)b->nblks / (double)std::max(nbk, 1));
-  const bool sparse_guess = E->force_symbolic == 3 || (E->force_symbolic == 0 && nbr >= 2048 && prod_est < 0.6 * (double)nbr * (double)nbc);
-  if (filtering && sparse_guess && !retain_sparsity) {
+  SymbolicSizes sizes;
+  sizes.nbr = nbr, sizes.nbk = nbk, sizes.nbc = nbc, sizes.a_nblks = a->nblks, sizes.b_nblks = b->nblks;
+  sizes.filtering = filtering, sizes.retain = retain_sparsity != 0, sizes.forced = E->force_symbolic;
+  SymbolicChoice sym = choose_symbolic_pattern(sizes);   // (mm_choose.h)
+  if (sym.bitmap_rows) {
     if (E->have_cin)
       ACC_CHECK(hipMemcpyAsync(E->c_bm.p, E->cin_bm.p, sizeof(uint32_t) * (size_t)nbr * W, hipMemcpyDeviceToDevice, st));
     else
@@ -498,10 +504,8 @@ int dbcsr_amd_mm_symbolic_filtered(void* handle, libsmm_acc_data_t datatype, dou
     if (ck > 0 && cn > 0) mean_k = sk / ck, mean_n = sn / cn;
   }
   const int64_t b_bytes_est = (int64_t)((double)b->nblks * mean_k * mean_n * (double)sizeof(double));
-  int NP = (int)std::min<int64_t>((b_bytes_est + E->panel_bytes - 1) / E->panel_bytes, (int64_t)W);
-  if (NP < 1) NP = 1;
-  const int PW = (W + NP - 1) / NP;
-  NP = (W + PW - 1) / PW;
+  int NP = 1, PW = W;
+  choose_panels(W, b_bytes_est, E->panel_bytes, &NP, &PW);
   const int R = (nbr + 7) / 8;
   // rows walked together per XCD.  Measured on config 2 (DBCSR_AMD_MM_ROW_GROUP = 1/2/4/6/8: 22.7/22.8/23.5/25.2/26.3 ms):
   // the B reuse it buys (10 % fill: 14 % fewer B fetches at 4 rows) does not pay for the extra A rows in L2 -> default 1.
@@ -532,13 +536,16 @@ int dbcsr_amd_mm_symbolic_filtered(void* handle, libsmm_acc_data_t datatype, dou
       E->c_blk_p_ws.ensure((size_t)c_nblks + 1))
     return -1;
   // 3. per C block: number of products, size; flop
-  // one lane per (row, column) candidate unless C is extremely sparse (then one thread per bitmap word)
+  // one lane per (row, column) candidate unless C is extremely sparse (then one thread per bitmap word); a sparse C with enough block rows to fill the
+  // chip: product-driven kernels (choose_symbolic_count, mm_choose.h)
   const int nJ = (nbc + 63) / 64;
-  E->grid_kernels = filtering || (((int64_t)nbr * nJ * 64 <= 256 * std::max<int64_t>(c_nblks, 1)) && !E->force_word_kernels);
-  // sparse C (less than 60 % of the candidates are blocks) with enough block rows to fill the chip: product-driven kernels
-  E->rows_kernels = E->force_symbolic == 3 || (E->force_symbolic == 0 && nbr >= 2048 && 10 * c_nblks < 6 * (int64_t)nbr * nbc);
+  sym = choose_symbolic_count(sizes, sym, c_nblks);
+  E->grid_kernels = sym.grid_kernels;
+  E->rows_kernels = sym.rows_kernels;
+  E->sym_bitmap = sym.bitmap_rows ? 2 : (filtering ? 1 : 0);
+  E->sym_NP = NP, E->sym_PW = PW;
+  E->sym_rowp_chunks = (int)(((int64_t)nbr + kScanChunk - 1) / kScanChunk);
   if (E->rows_kernels) {
-    E->grid_kernels = false;
     ACC_CHECK(hipMemsetAsync(E->prod_cnt.p, 0, sizeof(int) * (size_t)c_nblks, st));
     hipLaunchKernelGGL(block_sizes_rows, grid_for((int64_t)nbr * W), dim3(256), 0, st, E->c_bm.p, E->c_pre.p, c_out_row_p, a->row_blk_size,
                        b->col_blk_size, nbr, W, E->blk_nze.p);

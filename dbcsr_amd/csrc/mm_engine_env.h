@@ -30,10 +30,9 @@ static void engine_read_env(Engine* E) {
   if (const char* k = getenv("DBCSR_AMD_MM_BIG")) E->sw.use_big = atoi(k);
   if (const char* k = getenv("DBCSR_AMD_MM_MID")) E->sw.use_mid = atoi(k);
   if (const char* k = getenv("DBCSR_AMD_MM_SYMBOLIC")) {
-    E->force_word_kernels = strcmp(k, "word") == 0;
     E->force_symbolic = strcmp(k, "word") == 0 ? 1 : (strcmp(k, "grid") == 0 ? 2 : (strcmp(k, "rows") == 0 ? 3 : 0));
   }
-  if (const char* k = getenv("DBCSR_AMD_MM_PANEL_MB")) E->panel_bytes = (int64_t)atoll(k) << 20;
+  if (const char* k = getenv("DBCSR_AMD_MM_PANEL_MB")) E->panel_bytes = panel_bytes_of_mb(atoll(k));   // (at least 1 MB: choose_panels divides by it)
 #ifdef DBCSR_AMD_EXPERIMENTS
   // ---- the lab build's switches (every one selects something that was measured and does not win; see the top of this file) ----
   if (const char* k = getenv("DBCSR_AMD_MM_F32_GROUP")) {
@@ -41,7 +40,7 @@ static void engine_read_env(Engine* E) {
     E->lab.f32_group = (r >= 2 && r <= 4) ? r : (r < 0 ? -1 : 0);
   }
   if (const char* k = getenv("DBCSR_AMD_MM_F64_GROUP")) E->lab.f64_group = atoi(k);
-  if (const char* k = getenv("DBCSR_AMD_MM_GROUP_PANEL_MB")) E->ls.group_panel_bytes = (int64_t)atoll(k) << 20;
+  if (const char* k = getenv("DBCSR_AMD_MM_GROUP_PANEL_MB")) E->ls.group_panel_bytes = panel_bytes_of_mb(atoll(k));
   if (const char* k = getenv("DBCSR_AMD_MM_CLASS_G")) {
     const int g = atoi(k);
     E->lab.class_g = (g == 2 || g == 4 || g == 8) ? g : 1;

@@ -493,6 +493,16 @@ const char* dbcsr_amd_mm_last_kernel(void* handle) {
   return E ? E->last_kernel : "";
 }
 
+const char* dbcsr_amd_mm_last_symbolic(void* handle) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E) return "";
+  static const char* const bitmap[] = {"none", "plain", "filtered", "rows_filtered"};
+  snprintf(E->last_symbolic, sizeof E->last_symbolic, "bitmap=%s count=%s W=%d NP=%d PW=%d classes=%d rowp_chunks=%d plan=%s",
+           bitmap[std::min(std::max(E->sym_bitmap, -1), 2) + 1], E->sym_bitmap < 0 ? "none" : (E->rows_kernels ? "rows" : (E->grid_kernels ? "grid" : "word")),
+           E->W, E->sym_NP, E->sym_PW, E->facts.cls_mode ? 1 : 0, E->sym_rowp_chunks, E->plan_hit ? "hit" : "miss");
+  return E->last_symbolic;
+}
+
 int dbcsr_amd_mm_expect_filter(void* handle, double eps) {
   Engine* E = static_cast<Engine*>(handle);
   if (!E || !(eps >= 0.0)) return -1;

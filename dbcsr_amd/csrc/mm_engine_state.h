@@ -28,7 +28,7 @@ struct LabState {
   // group kernels (mm_group.h, mm_group64.h)
   int group_R = 0;
   bool group_built = false, b_monotone = false;
-  int64_t group_panel_bytes = 0;   // DBCSR_AMD_MM_GROUP_PANEL_MB: target size of a B column panel of the group launch (0: panel_bytes)
+  int64_t group_panel_bytes = 0;   // DBCSR_AMD_MM_GROUP_PANEL_MB: target size of a B column panel of the group launch (unset: panel_bytes; at least 1 MB)
   DevBuf<int> groups, group_flag, group_cnt;
   DevBuf<GWork> group_work;
   DevBuf<GEntry> group_entries;
@@ -106,6 +106,10 @@ struct Engine {
   bool have_cin = false, valid = false;
   bool rows_kernels = false;  // product-driven symbolic kernels (sparse C); DBCSR_AMD_MM_SYMBOLIC=rows forces, =grid / =word exclude
   bool grid_kernels = false;
+  // what the symbolic phase chose (mm_choose.h: choose_symbolic_pattern / _count, choose_panels), for dbcsr_amd_mm_last_symbolic: the pattern kernel
+  // (-1 none: no block row or column, 0 c_bitmap, 1 c_bitmap_filtered, 2 c_bitmap_rows_filtered), the column panels, the chunks of the scan that made row_p
+  int sym_bitmap = -1, sym_NP = 0, sym_PW = 0, sym_rowp_chunks = 0;
+  char last_symbolic[160] = "";
   int64_t cls_len[kNumClasses] = {0}, cls_off[kNumClasses] = {0};
   FilterArgs filter = {nullptr, nullptr, 0.0f};
   double drop_pending = 0.0;       // dbcsr_amd_mm_expect_filter: eps^2 of the final block filter announced for the next numeric phase (0: none)
@@ -154,8 +158,7 @@ struct Engine {
   Switches sw;      // the numeric phase's kernel families (mm_choose.h)
   LabSwitches lab;  // lab build only: no state in the shipping build
   int use_plan = 1;  // DBCSR_AMD_MM_PLAN=0: every multiply runs its symbolic phase
-  int force_symbolic = 0;     // DBCSR_AMD_MM_SYMBOLIC: 0 automatic, 1 word, 2 grid, 3 rows
-  bool force_word_kernels = false;  // DBCSR_AMD_MM_SYMBOLIC=word forces the per-word symbolic kernels
+  int force_symbolic = 0;     // DBCSR_AMD_MM_SYMBOLIC: 0 automatic, 1 word (the per-word kernels), 2 grid, 3 rows (SymbolicSizes::forced, mm_choose.h)
   int64_t panel_bytes = 256ll << 20;  // DBCSR_AMD_MM_PANEL_MB: target size of a B column panel (config 2, round 3: 160 / 200 / 256 / 320 / 400 MB ->
                                       // 18.97 / 18.76 / 18.63 / 18.95 / 19.04 ms, profiles/r03_panel_wgwaves_sweep.txt)
 

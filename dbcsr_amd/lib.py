@@ -29,7 +29,7 @@ LIBSMM_SYMBOLS = [
 ]
 MM_SYMBOLS = [
     "dbcsr_amd_mm_create", "dbcsr_amd_mm_destroy", "dbcsr_amd_mm_symbolic", "dbcsr_amd_mm_numeric", "dbcsr_amd_bcsr_transpose",
-    "dbcsr_amd_bcsr_checksum", "dbcsr_amd_bcsr_fill_random", "dbcsr_amd_mm_kernel_name", "dbcsr_amd_mm_last_kernel", "dbcsr_amd_fabric_probe", "dbcsr_amd_mm_plan_stats", "dbcsr_amd_mm_trust_plan", "dbcsr_amd_mm_expect_filter", "dbcsr_amd_mm_stats", "dbcsr_amd_mm_timing", "dbcsr_amd_mm_init_c", "dbcsr_amd_bcsr_fill_random_dist",
+    "dbcsr_amd_bcsr_checksum", "dbcsr_amd_bcsr_fill_random", "dbcsr_amd_mm_kernel_name", "dbcsr_amd_mm_last_kernel", "dbcsr_amd_mm_last_symbolic", "dbcsr_amd_fabric_probe", "dbcsr_amd_mm_plan_stats", "dbcsr_amd_mm_trust_plan", "dbcsr_amd_mm_expect_filter", "dbcsr_amd_mm_stats", "dbcsr_amd_mm_timing", "dbcsr_amd_mm_init_c", "dbcsr_amd_bcsr_fill_random_dist",
     "dbcsr_amd_mm_symbolic_filtered", "dbcsr_amd_bcsr_filter_count", "dbcsr_amd_bcsr_filter_apply",
     "dbcsr_amd_bcsr_crop_count", "dbcsr_amd_bcsr_crop_apply", "dbcsr_amd_bcsr_scale_window",
     "dbcsr_amd_multiply", "dbcsr_amd_bcsr_release", "dbcsr_amd_bcsr_desymmetrize_count", "dbcsr_amd_bcsr_desymmetrize_apply",
@@ -183,6 +183,8 @@ def load_library(lab=False):
     L.dbcsr_amd_comm_allgather.argtypes = [vp, vp, vp, i64, vp]
     L.dbcsr_amd_mm_last_kernel.argtypes = [vp]
     L.dbcsr_amd_mm_last_kernel.restype = C.c_char_p
+    L.dbcsr_amd_mm_last_symbolic.argtypes = [vp]
+    L.dbcsr_amd_mm_last_symbolic.restype = C.c_char_p
     L.dbcsr_amd_smm_last_kernel.argtypes = []
     L.dbcsr_amd_smm_last_kernel.restype = C.c_char_p
     L.dbcsr_amd_fabric_probe.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]

@@ -127,6 +127,12 @@ class MultiplyEngine:
         v = self.L.dbcsr_amd_mm_last_kernel((eng or self).h)
         return v.decode() if v else ""
 
+    def last_symbolic(self):
+        """what the last symbolic phase chose, one line (dbcsr_amd_mm_last_symbolic): 'bitmap=... count=word|grid|rows W=.. NP=.. PW=.. classes=.. rowp_chunks=..
+        plan=miss|hit'; with k passes: the symbolic phase of the whole product"""
+        v = self.L.dbcsr_amd_mm_last_symbolic(self.h)
+        return v.decode() if v else ""
+
     def plan_stats(self):
         """(multiplies that reused the previous plan, multiplies that ran their symbolic phase) since the engine was made"""
         a, b = C.c_int64(), C.c_int64()

@@ -279,6 +279,10 @@ int dbcsr_amd_mm_stats(void* handle, dbcsr_amd_mnk_stat* out, int max_entries, i
 const char* dbcsr_amd_mm_kernel_name(libsmm_acc_data_t datatype);
 /* name (with its template arguments) of the block-product kernel the last dbcsr_amd_mm_numeric of this handle launched */
 const char* dbcsr_amd_mm_last_kernel(void* handle);
+/* what the last symbolic phase of this handle chose, one line: "bitmap=plain|filtered|rows_filtered count=word|grid|rows W=<bitmap words per row>
+   NP=<column panels> PW=<words per panel> classes=0|1 rowp_chunks=<chunks of the scan that made row_p> plan=miss|hit" (plan=hit: the saved plan of the
+   previous multiply was reused, the other fields are that plan's).  Read-only; the text lives in the handle until the next call. */
+const char* dbcsr_amd_mm_last_symbolic(void* handle);
 /* name of the stack kernel the calling thread's last libsmm_acc_process (fp64, homogeneous stack) launched: "smm_stack_f64_exact<m,n,k>" (compiled
    for the triplet at run time, as libsmm_acc.cpp:90-195 does), "smm_stack_f64_lds(...)" (run-time sizes), "smm_stack_f64_big(...)" (blocks of 33 ... 80) */
 const char* dbcsr_amd_smm_last_kernel(void);
