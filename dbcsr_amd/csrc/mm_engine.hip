@@ -38,7 +38,7 @@
 //   mm_engine_ops.h      init_c, crop, filter, checksum, fill, transpose, twin moves, statistics
 //   mm_engine_algebra.h  add (count / apply), add_on_diag pieces, trace, dot, norm, norms and vectors, matvec, multivec, rank update (kernels: mm_algebra.h,
 //                        mm_multivec.h, mm_rank_update.h, over the block walk of mm_block_walk.h), the block diagonal (mm_block_inverse.h), its product with a
-//                        matrix (mm_block_scale.h) and the dense conversion (mm_dense.h)
+//                        matrix (mm_block_scale.h), the dense conversion (mm_dense.h) and the submatrix method (mm_submatrix.h)
 // This file: create / destroy, the symbolic phase, and the numeric phase as a sequence -- product lists, choice, set-up, launch, plan bookkeeping.
 #include <hip/hip_runtime.h>
 
@@ -71,6 +71,7 @@
 #include "mm_block_inverse.h"  // the block diagonal: its copy and the batched inverse of its blocks
 #include "mm_block_scale.h"  // a block diagonal applied to a matrix in place
 #include "mm_dense.h"  // dense <-> block-sparse: to_dense, from_dense and the count half of create_from_dense
+#include "mm_submatrix.h"  // the submatrix method: batched dense principal submatrices out of the matrix and back onto its pattern
 // The library comes in two builds (Makefile): the SHIPPING one holds what a multiply can run by itself -- the kernels listed above, their
 // symbolic phases, plan reuse -- and the LAB one (-DDBCSR_AMD_EXPERIMENTS, libdbcsr_acc_amd_lab.so) adds every dataflow and variant that
 // was built, made parity-green and measured but does not win: the LDS-DMA ring kernels (mm_dma.h), XCD-wide C tiles (mm_tile.*), CU-wide

@@ -2,7 +2,8 @@
 // dbcsr_amd_bcsr_add_count / _add_apply, the pieces of dbcsr_add_on_diag (dbcsr_amd_bcsr_diag_count / _diag_fill / _diag_shift), dbcsr_amd_bcsr_trace,
 // _dot, _norm2, and the norms and vectors: dbcsr_amd_bcsr_maxabs, _row_sums, _col_sums, _gershgorin, _get_diag, _set_diag, _scale_by_vector, _matvec, _multivec, _rank_update,
 // the block diagonal: dbcsr_amd_bcsr_block_diag_count / _apply / _invert / _multiply, and the dense conversion: dbcsr_amd_bcsr_to_dense / _from_dense_apply /
-// _from_dense_count.  Kernels: mm_algebra.h, mm_multivec.h, mm_rank_update.h, mm_block_inverse.h, mm_block_scale.h, mm_dense.h. The reductions, the diagonal pieces, the same-pattern add and the norms and vectors use buffers of their own (Engine::alg_*) and the
+// _from_dense_count, and the submatrix method: dbcsr_amd_bcsr_submatrix_gather / _submatrix_scatter.
+// Kernels: mm_algebra.h, mm_multivec.h, mm_rank_update.h, mm_block_inverse.h, mm_block_scale.h, mm_dense.h, mm_submatrix.h. The reductions, the diagonal pieces, the same-pattern add and the norms and vectors use buffers of their own (Engine::alg_*) and the
 // scan's scratch, which no saved plan depends on (the checksum uses it the same way): they do NOT invalidate the plan.  The union add borrows the
 // symbolic phase's bitmaps and prefix arrays and invalidates it, as filter and crop do.
 #ifndef DBCSR_AMD_MM_ENGINE_ALGEBRA_H
@@ -1011,6 +1012,79 @@ int dbcsr_amd_bcsr_from_dense_count(void* handle, libsmm_acc_data_t datatype, co
   *nblks = E->host_scalars[0];
   *nze = E->host_scalars[1];
   return check(hipGetLastError(), "dbcsr_amd_bcsr_from_dense_count", __FILE__, __LINE__);
+}
+// ---- submatrix method (kernels: mm_submatrix.h) ---------------------------------------------------------------------------------------------------------------
+// Pure data movement by the caller's index sets: no buffer of the engine is used, no saved plan is touched, nothing synchronises.
+extern "C++" {
+// member columns per workgroup of submatrix_gather: about 8192 elements of the window, at most 64 tiles (dense_group's rule, with the mean member size
+// n / max_members for the mean block size)
+static inline int submatrix_group(int64_t n, int max_members) {
+  if (max_members <= 0) return 1;
+  const int64_t side = std::max<int64_t>(1, n / max_members), tile = side * side;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(8192 / tile, 64), max_members));
+}
+
+constexpr int kSubmatrixSlotsPerLaunch = 65535;   // (gridDim.y)
+
+template <typename T>
+static void submatrix_gather_launch(hipStream_t st, const dbcsr_amd_bcsr* m, int kind, int nsub, const int32_t* set_ptr, const int32_t* set_idx,
+                                    const int32_t* set_off, const int32_t* sub_dim, int nslot, const int32_t* slot_sub, int max_members, void* dense,
+                                    int64_t n, int64_t ld, int64_t batch_stride, double pad_diag) {
+  const int G = submatrix_group(n, max_members), NG = std::max(1, (max_members + G - 1) / G);
+  const unsigned gx = (unsigned)(((int64_t)max_members + 1) * NG);
+  for (int slot0 = 0; slot0 < nslot; slot0 += kSubmatrixSlotsPerLaunch)
+    hipLaunchKernelGGL((submatrix_gather<T>), dim3(gx, (unsigned)std::min(nslot - slot0, kSubmatrixSlotsPerLaunch)), dim3(256), 0, st, m->row_p, m->col_i,
+                       m->blk_p, static_cast<const T*>(m->data), m->row_blk_size, m->col_blk_size, m->nblkrows, kind, aligned16(m->data), nsub, set_ptr,
+                       set_idx, set_off, sub_dim, slot_sub, slot0, G, NG, static_cast<T*>(dense), (int)n, ld, batch_stride, pad_diag);
+}
+
+template <typename T>
+static void submatrix_scatter_launch(hipStream_t st, dbcsr_amd_bcsr* m, int S, int nsub, const int32_t* set_ptr, const int32_t* set_idx,
+                                     const int32_t* set_off, const int32_t* owner, const int32_t* sub_slot, const void* dense, int64_t n, int64_t ld,
+                                     int64_t batch_stride) {
+  hipLaunchKernelGGL((submatrix_scatter<T>), dim3((unsigned)((int64_t)m->nblkrows * S)), dim3(256), 0, st, m->row_p, m->col_i, m->blk_p,
+                     static_cast<T*>(m->data), m->row_blk_size, m->col_blk_size, m->nblkrows, S, aligned16(m->data), nsub, set_ptr, set_idx, set_off, owner,
+                     sub_slot, static_cast<const T*>(dense), (int)n, ld, batch_stride);
+}
+}  // extern "C++"
+
+int dbcsr_amd_bcsr_submatrix_gather(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, int kind, int nsub, const int32_t* set_ptr,
+                                    const int32_t* set_idx, const int32_t* set_off, const int32_t* sub_dim, int nslot, const int32_t* slot_sub,
+                                    int max_members, void* dense, int64_t n, int64_t ld, int64_t batch_stride, double pad_diag, void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E || !m || kind < -1 || kind > 3 || m->nblkrows != m->nblkcols) return -1;
+  if (nsub < 0 || nslot < 0 || max_members < 0 || n < 0 || n > INT32_MAX || ld < n) return -1;
+  if (nslot > 1 && (batch_stride < 0 || (n > 0 && batch_stride / n < ld))) return -1;   // (batch_stride < n ld, without forming the product)
+  if (nslot > 0 && n > 0) {   // (a null tensor: only with an empty batch)
+    if (!dense || (nsub > 0 && (!set_ptr || !sub_dim)) || (max_members > 0 && (!set_idx || !set_off))) return -1;
+    if (m->nblks > 0 && (!m->row_p || !m->col_i || !m->blk_p || !m->data)) return -1;
+  }
+  if (!algebra_type(datatype)) return -10;
+  if (nslot == 0 || n == 0) return 0;
+  hipStream_t st = stream_of(stream);
+  const int G = submatrix_group(n, max_members);
+  if (((int64_t)max_members + 1) * std::max(1, (max_members + G - 1) / G) > INT32_MAX) return -1;   // (the grid)
+  DBCSR_AMD_BY_TYPE(submatrix_gather_launch, st, m, kind, nsub, set_ptr, set_idx, set_off, sub_dim, nslot, slot_sub, max_members, dense, n, ld, batch_stride,
+                    pad_diag);
+  return check(hipGetLastError(), "dbcsr_amd_bcsr_submatrix_gather", __FILE__, __LINE__);
+}
+
+int dbcsr_amd_bcsr_submatrix_scatter(void* handle, libsmm_acc_data_t datatype, const void* dense, int64_t n, int64_t ld, int64_t batch_stride, int nsub,
+                                     const int32_t* set_ptr, const int32_t* set_idx, const int32_t* set_off, const int32_t* owner, const int32_t* sub_slot,
+                                     dbcsr_amd_bcsr* m, void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E || !m || m->nblkrows != m->nblkcols) return -1;
+  if (nsub < 0 || n < 0 || n > INT32_MAX || ld < n || batch_stride < 0) return -1;
+  const bool work = n > 0 && nsub > 0 && m->nblks > 0 && m->nblkrows > 0;
+  if (work && (!dense || !set_ptr || !set_idx || !set_off || !owner || !sub_slot)) return -1;   // (a null tensor: only with nothing to move)
+  if (!algebra_type(datatype)) return -10;
+  engine_writes_values(E);
+  if (!work) return 0;
+  hipStream_t st = stream_of(stream);
+  const int S = algebra_split(m->nblkrows, m->nblks);
+  if ((int64_t)m->nblkrows * S > INT32_MAX) return -1;   // (the grid)
+  DBCSR_AMD_BY_TYPE(submatrix_scatter_launch, st, m, S, nsub, set_ptr, set_idx, set_off, owner, sub_slot, dense, n, ld, batch_stride);
+  return check(hipGetLastError(), "dbcsr_amd_bcsr_submatrix_scatter", __FILE__, __LINE__);
 }
 #undef DBCSR_AMD_BY_TYPE
 

@@ -519,6 +519,38 @@ int dbcsr_amd_bcsr_from_dense_count(void* handle, libsmm_acc_data_t datatype, co
   const int32_t* row_blk_size, const int32_t* col_blk_size, int nblkrows, int nblkcols, double eps, int32_t* dst_row_p, int32_t* dst_col_i,
   int64_t* dst_blk_p, int64_t* nblks, int64_t* nze, void* stream);
 
+/* Submatrix method: the data movement of "a dense function of a large sparse matrix, one small dense principal submatrix per block column (or group of
+ * block columns) at a time" -- batched windows out of the matrix and back onto its pattern, without leaving the device.  Not a mirror of a routine of the
+ * reference.  m has a square block structure whose row block sizes are its column block sizes (nblkrows != nblkcols: -1; equal sizes are the caller's
+ * contract).  The index sets are the caller's (device, int32): submatrix g = 0 ... nsub - 1 is the ascending set of block rows set_idx[set_ptr[g] ...
+ * set_ptr[g + 1]), set_off [as set_idx] the element offset of each member inside the submatrix (the running sum of the members' block sizes), sub_dim
+ * [nsub] its side n_g; owner [nblkcols] the submatrix that block column belongs to, -1 for none.  `dense` is a batch of windows of n x n elements of the
+ * data type, one per slot, row by row: element (i, j) of slot t at t * batch_stride + i * ld + j, every offset formed in 64 bits.  Same types as the
+ * algebra above (-10 for another type code).  -1 for a null handle or matrix, a negative count, n above 2^31 - 1, ld < n, batch_stride < n * ld with
+ * more than one slot (_gather; _scatter: batch_stride < 0), a kind outside -1 ... 3, and a null tensor with a non-empty batch; 0 with nothing written for
+ * nslot == 0 or n == 0 (_scatter: also nsub == 0 or a matrix without blocks).  Both are asynchronous on stream and synchronise nothing; they use no
+ * buffer of the engine, no saved plan is touched.  No atomics, no memset; the same bits on every call.  The tensor must not overlap the data area of m
+ * (the caller's contract).  Sets that do not fit the matrix give wrong values but never an access outside the windows: a member outside the block
+ * structure, or whose run set_off + size passes n, is skipped whole, and a submatrix id outside 0 ... nsub - 1 counts as an empty set.
+ *   _submatrix_gather   slot t = 0 ... nslot - 1 holds submatrix g = slot_sub[t] (slot_sub null: g = t).  Its window receives every tile (a, b) of
+ *     S_g x S_g that m stores at (set_off[a], set_off[b]), bit for bit; for kind 0 ... 3 (S A H K) the twin of the block stored at (b, a) where (a, b) is
+ *     not stored (transposed; bit 0 of kind negates, bit 1 conjugates: sign flips, exact), a diagonal block taken in full as stored -- _to_dense's
+ *     reading; +0.0 everywhere else inside n_g x n_g; outside n_g x n_g and inside n x n, +0.0 off the diagonal and pad_diag on it (complex:
+ *     (pad_diag, 0)), so that the window is blockdiag(A[S, S], pad_diag I).  Every element of every window is written exactly once per call, a window
+ *     of a set without members included; nothing outside a window is written: the columns n ... ld - 1 and whatever lies between two windows keep
+ *     their bits.  max_members: the largest number of members among the submatrices of the batch (or of all).  m is only read.
+ *   _submatrix_scatter  every block (R, C) the index of m names with g = owner[C] >= 0, t = sub_slot[g] >= 0 (sub_slot [nsub]: the slot that holds
+ *     submatrix g, -1 for none) and R a member of S_g (binary search) <- the elements at (set_off[pos R], set_off[pos C]) of window t, bit for bit.
+ *     Everything else keeps its bits: blocks of block columns without an owner or whose submatrix has no slot, blocks whose row is no member, the holes
+ *     of an unpacked matrix, every index array.  No symmetry is applied: of a stored triangle the blocks stored are taken from where they lie.  The
+ *     norms a numeric phase announced are forgotten. */
+int dbcsr_amd_bcsr_submatrix_gather(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, int kind, int nsub, const int32_t* set_ptr,
+  const int32_t* set_idx, const int32_t* set_off, const int32_t* sub_dim, int nslot, const int32_t* slot_sub, int max_members, void* dense, int64_t n,
+  int64_t ld, int64_t batch_stride, double pad_diag, void* stream);
+int dbcsr_amd_bcsr_submatrix_scatter(void* handle, libsmm_acc_data_t datatype, const void* dense, int64_t n, int64_t ld, int64_t batch_stride, int nsub,
+  const int32_t* set_ptr, const int32_t* set_idx, const int32_t* set_off, const int32_t* owner, const int32_t* sub_slot, dbcsr_amd_bcsr* m,
+  void* stream);
+
 /* Measurement helper (bench.py, roofline.fabric): what the L2 <-> Infinity-Cache fabric of the current device delivers, in TB/s -- a
  * plain streaming read of a 160 MB window by all CUs, and the block gather of the block-product dataflow (4232-byte blocks from
  * pseudo-random places of the window into LDS, whole 128-byte lines counted).  Takes well under a second; synchronises the device. */

@@ -81,6 +81,14 @@ one call per sample) against dbcsr_to_dense timed the same way.  The condition: 
 
     python tools/ops_bench.py --dense --alternations 7 --warmup 2 --out profiles/dense_conversion.txt
 
+With --submatrix only the submatrix method's two copies are timed (dbcsr_submatrix_gather, dbcsr_submatrix_scatter; kernels of
+dbcsr_amd/csrc/mm_submatrix.h) on the matrix of --dense at one block in ten: with one submatrix per block column, gather into the whole batch padded to
+the largest side, scatter out of it, and zero_() of the batch as the floor of writing it; and the full-set gather (one submatrix holding every block
+row) against dbcsr_to_dense of the same matrix, which moves the same bytes with the same moves, alternating in one process.  No condition: the ratio and
+its spread are the result:
+
+    python tools/ops_bench.py --submatrix --alternations 7 --warmup 2 --out profiles/submatrix.txt
+
 A sample is `--reps` calls back to back between two device events, divided by reps.  Bytes are counted from the shapes: 8 * (elements read + elements
 written) of the data areas, index arrays left out.  Spread = (max - min) / median over the samples."""
 import argparse
@@ -98,6 +106,7 @@ from dbcsr_amd.matrix import DbcsrMatrix, StreamHandle  # noqa: E402
 from dbcsr_amd.multiply import MultiplyEngine, dbcsr_multiply  # noqa: E402
 from dbcsr_amd.operations import dbcsr_add, dbcsr_get_block_diag, dbcsr_invert_block_diag, dbcsr_scale, dbcsr_scale_by_block_diag  # noqa: E402
 from dbcsr_amd.operations import dbcsr_create_from_dense, dbcsr_from_dense, dbcsr_to_dense  # noqa: E402
+from dbcsr_amd.submatrix import dbcsr_submatrix_gather, dbcsr_submatrix_plan, dbcsr_submatrix_scatter  # noqa: E402
 
 
 def matrix_of(mask, b, seed):
@@ -573,6 +582,74 @@ def dense_conversion(args, say, lines, rng):
             f.write("\n".join(lines) + "\n")
 
 
+def submatrix(args, say, lines, rng):
+    """the submatrix method's two copies on the matrix of the dense conversion, and the full-set gather against dbcsr_to_dense"""
+    E = MultiplyEngine()
+    b, nb = 23, 504
+    n_full = b * nb
+    M = matrix_of(rng.random((nb, nb)) < 0.1, b, 40)
+    # one submatrix per block column
+    plan = dbcsr_submatrix_plan(M)
+    n = plan.max_dim
+    batch = torch.full((plan.nsub, n, n), float("nan"), dtype=torch.float64, device="cuda")
+    dbcsr_submatrix_gather(M, plan, pad_diag=1.0, out=batch, engine=E)
+    D = dbcsr_to_dense(M, engine=E)
+    # what is timed is right: some windows against index_select of the whole dense matrix, bit for bit (the whole comparison is the tests' business)
+    set_ptr, set_idx = plan.set_ptr.cpu().numpy(), plan.set_idx.cpu().numpy()
+    for g in (0, nb // 2, nb - 1):
+        S = set_idx[set_ptr[g]:set_ptr[g + 1]]
+        e = torch.as_tensor((S[:, None].astype(np.int64) * b + np.arange(b)).reshape(-1)).cuda()
+        ng = int(e.numel())
+        if ng != int(plan.sub_dim_host[g]) or not torch.equal(batch[g, :ng, :ng], D[e][:, e]) or bool(torch.isnan(batch[g]).any()):
+            sys.exit("dbcsr_submatrix_gather is wrong: nothing is timed")
+    X = M.copy()
+    dbcsr_submatrix_scatter(batch, X, plan, engine=E)
+    if not torch.equal(X.data, M.data):
+        sys.exit("dbcsr_submatrix_scatter is wrong: nothing is timed")
+    filled = int((plan.sub_dim_host ** 2).sum())
+    say("")
+    say("%d x %d blocks of %d x %d, fill 0.10: %d blocks, %.1f MB of blocks; one submatrix per block column: %d windows, sides %d ... %d, %d members at most"
+        % (nb, nb, b, b, M.nblks, 8e-6 * M.nze, plan.nsub, int(plan.sub_dim_host.min()), n, plan.max_members))
+    say("the batch (%d, %d, %d): %.1f MB, of which %.1f MB inside the submatrices (%.1f %% padding)"
+        % (plan.nsub, n, n, 8e-6 * plan.nsub * n * n, 8e-6 * filled, 100.0 * (1 - filled / (plan.nsub * n * n))))
+    # the full set: one submatrix holding every block row, against dbcsr_to_dense of the same matrix
+    whole = dbcsr_submatrix_plan(M, [0] * nb)
+    out_s = torch.full((1, n_full, n_full), float("nan"), dtype=torch.float64, device="cuda")
+    dbcsr_submatrix_gather(M, whole, out=out_s, engine=E)
+    if not torch.equal(out_s[0], D):
+        sys.exit("the full-set gather is not dbcsr_to_dense: nothing is timed")
+    run = {
+        "gather": lambda: dbcsr_submatrix_gather(M, plan, pad_diag=1.0, out=batch, engine=E),
+        "scatter": lambda: dbcsr_submatrix_scatter(batch, X, plan, engine=E),
+        "zeros(batch)": lambda: batch.zero_(),
+        "full-set gather": lambda: dbcsr_submatrix_gather(M, whole, out=out_s, engine=E),
+        "to_dense": lambda: dbcsr_to_dense(M, out=D, engine=E),
+    }
+    moved = {"gather": plan.nsub * n * n, "scatter": 2 * M.nze, "zeros(batch)": plan.nsub * n * n, "full-set gather": n_full * n_full + M.nze,
+             "to_dense": n_full * n_full + M.nze}
+    times = {k: [] for k in run}
+    for step in range(args.warmup + args.alternations):
+        for k in run:
+            x = sample(run[k], args.reps)
+            if step >= args.warmup:
+                times[k].append(x)
+    dbcsr_submatrix_gather(M, plan, pad_diag=1.0, out=batch, engine=E)   # (zeros(batch) ran last on it)
+    med = {}
+    for k in run:
+        v = sorted(times[k])
+        med[k] = v[len(v) // 2]
+        say("  %-16s median %9.4f ms  min %9.4f  max %9.4f  spread %5.1f %%  %8.1f GB/s   samples: %s"
+            % (k, med[k], v[0], v[-1], 100 * (v[-1] - v[0]) / med[k], 8e-6 * moved[k] / med[k], " ".join("%.4f" % x for x in times[k])))
+    say("  (GB/s: gather and zeros by the batch's bytes written, scatter by the blocks read and written, the two full matrices by window + blocks)")
+    r = sorted(x / z for x, z in zip(times["full-set gather"], times["to_dense"]))
+    say("  full-set gather / to_dense: median of medians %.3f; per alternation %.3f ... %.3f (median %.3f, spread %.1f %%)"
+        % (med["full-set gather"] / med["to_dense"], r[0], r[-1], r[len(r) // 2], 100 * (r[-1] - r[0]) / r[len(r) // 2]))
+    say("  gather / zeros(batch): %.2f" % (med["gather"] / med["zeros(batch)"]))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=32768)
@@ -589,6 +666,7 @@ def main():
     ap.add_argument("--block-inverse", action="store_true", help="only the block diagonal: get_block_diag, invert_block_diag and what they replace")
     ap.add_argument("--block-scale", action="store_true", help="only the block diagonal applied to a matrix: left, right, both, dbcsr_scale and the multiply it replaces")
     ap.add_argument("--dense", action="store_true", help="only the dense conversion: to_dense, from_dense, create_from_dense and what they replace")
+    ap.add_argument("--submatrix", action="store_true", help="only the submatrix method: gather, scatter, and the full-set gather against to_dense")
     ap.add_argument("--mfma-tflops", type=float, default=None, help="with --rank-update / --block-scale: the fp64 MFMA figure bench.py --full measured in the same session")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     args = ap.parse_args()
@@ -613,6 +691,8 @@ def main():
         return block_scale(args, say, lines, rng)
     if args.dense:
         return dense_conversion(args, say, lines, rng)
+    if args.submatrix:
+        return submatrix(args, say, lines, rng)
     only =("norm", "norm.T", "matvec.N", "matvec.T", "matvec.S", "gersh.N", "colnorm", "gersh.S") if args.matvec else None
     # the same-pattern pair
     mask = rng.random((nb, nb)) < args.fill_flat
