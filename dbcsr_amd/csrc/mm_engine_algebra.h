@@ -118,6 +118,27 @@ static int reduce_finish(Engine* E, hipStream_t st, int64_t nw, double out2[2], 
   memcpy(out2, E->host_scalars + 4, 2 * sizeof(double));
   return check(hipGetLastError(), what, __FILE__, __LINE__);
 }
+
+// Do A and B, both with na blocks, have the same pattern at the same offsets, and is A packed?  algebra_compare's flags (0: yes) and the end of A's last
+// block, brought to the host (one small kernel, one flag; synchronises; a saved plan is not touched).  The callers made alg_i32 hold 4 and alg_i64 8 entries.
+static int same_index_packed(Engine* E, hipStream_t st, const dbcsr_amd_bcsr* a, const dbcsr_amd_bcsr* b, int* flags, int64_t* packed_nze) {
+  const int nbr = a->nblkrows;
+  const int64_t na = a->nblks;
+  *flags = 0;
+  *packed_nze = 0;
+  if (na <= 0 || nbr <= 0) return 0;
+  ACC_CHECK(hipMemsetAsync(E->alg_i32.p, 0, sizeof(int), st));
+  ACC_CHECK(hipMemsetAsync(E->alg_i64.p, 0, sizeof(int64_t), st));
+  const int S = std::max(1, row_split(nbr, na / 64));   // (a lane per block: a wave covers 64 of them)
+  hipLaunchKernelGGL(algebra_compare, grid_for((int64_t)nbr * S * 64), dim3(256), 0, st, a->row_p, a->col_i, a->blk_p, b->row_p, b->col_i, b->blk_p,
+                     a->row_blk_size, a->col_blk_size, nbr, S, na, E->alg_i32.p, E->alg_i64.p);
+  ACC_CHECK(hipMemcpyAsync(E->host_scalars, E->alg_i32.p, sizeof(int), hipMemcpyDeviceToHost, st));
+  ACC_CHECK(hipMemcpyAsync(E->host_scalars + 1, E->alg_i64.p, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  ACC_CHECK(hipStreamSynchronize(st));
+  *flags = *reinterpret_cast<const int*>(E->host_scalars);
+  *packed_nze = E->host_scalars[1];
+  return 0;
+}
 }  // extern "C++"
 
 int dbcsr_amd_bcsr_add_count(void* handle, const dbcsr_amd_bcsr* a, const dbcsr_amd_bcsr* b, int beta_is_zero, int32_t* dst_row_p, int64_t* nblks,
@@ -138,18 +159,7 @@ int dbcsr_amd_bcsr_add_count(void* handle, const dbcsr_amd_bcsr* a, const dbcsr_
   if (!beta_is_zero && na == nb) {
     int flags = 0;
     int64_t packed_nze = 0;
-    if (na > 0 && nbr > 0) {
-      ACC_CHECK(hipMemsetAsync(E->alg_i32.p, 0, sizeof(int), st));
-      ACC_CHECK(hipMemsetAsync(E->alg_i64.p, 0, sizeof(int64_t), st));
-      const int S = std::max(1, row_split(nbr, na / 64));   // (a lane per block: a wave covers 64 of them)
-      hipLaunchKernelGGL(algebra_compare, grid_for((int64_t)nbr * S * 64), dim3(256), 0, st, a->row_p, a->col_i, a->blk_p, b->row_p, b->col_i, b->blk_p,
-                         a->row_blk_size, a->col_blk_size, nbr, S, na, E->alg_i32.p, E->alg_i64.p);
-      ACC_CHECK(hipMemcpyAsync(E->host_scalars, E->alg_i32.p, sizeof(int), hipMemcpyDeviceToHost, st));
-      ACC_CHECK(hipMemcpyAsync(E->host_scalars + 1, E->alg_i64.p, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-      ACC_CHECK(hipStreamSynchronize(st));
-      flags = *reinterpret_cast<const int*>(E->host_scalars);
-      packed_nze = E->host_scalars[1];
-    }
+    if (same_index_packed(E, st, a, b, &flags, &packed_nze)) return -1;
     if (flags == 0) {
       if (dst_row_p != a->row_p) ACC_CHECK(hipMemcpyAsync(dst_row_p, a->row_p, sizeof(int32_t) * ((size_t)nbr + 1), hipMemcpyDeviceToDevice, st));
       E->add_mode = 1;
@@ -1086,6 +1096,6 @@ int dbcsr_amd_bcsr_submatrix_scatter(void* handle, libsmm_acc_data_t datatype, c
   DBCSR_AMD_BY_TYPE(submatrix_scatter_launch, st, m, S, nsub, set_ptr, set_idx, set_off, owner, sub_slot, dense, n, ld, batch_stride);
   return check(hipGetLastError(), "dbcsr_amd_bcsr_submatrix_scatter", __FILE__, __LINE__);
 }
-#undef DBCSR_AMD_BY_TYPE
+// (DBCSR_AMD_BY_TYPE stays defined for mm_engine_elementwise.h, which follows this file and ends its life)
 
 #endif

@@ -154,6 +154,14 @@ struct Engine {
   int add_beta_zero = 0;
   int64_t add_nblks_a = 0, add_nblks_b = 0, add_nblks = 0, add_nze = 0;
 
+  // ---- element-wise operations on two patterns (mm_engine_elementwise.h): what dbcsr_amd_bcsr_hadamard_count leaves for its _apply, in buffers and fields
+  // that no other entry writes -- an add, a norm or a multiply between the two halves changes nothing here, and these change nothing of theirs ----
+  DevBuf<int> ew_i32;         // partner[nblks of A], blk_nze[nblks of A], row_cnt[nblkrows]
+  DevBuf<int64_t> ew_i64;     // off[nblks of A]: the result offset of every kept block of A; behind it src[2 * nblks of the result] (sized for all of A)
+  int had_mode = 0;           // what the last dbcsr_amd_bcsr_hadamard_count found: 0 nothing pending, 1 same pattern (flat pass), 2 two patterns
+  int had_assumed = 0;
+  int64_t had_nblks_a = 0, had_nblks_b = 0, had_nblks = 0, had_nze = 0;
+
   // ---- switches (mm_engine_env.h) ----
   Switches sw;      // the numeric phase's kernel families (mm_choose.h)
   LabSwitches lab;  // lab build only: no state in the shipping build

@@ -54,6 +54,8 @@ MM_SYMBOLS = [
     "dbcsr_amd_bcsr_to_dense", "dbcsr_amd_bcsr_from_dense_apply", "dbcsr_amd_bcsr_from_dense_count",
     # submatrix method (dbcsr_amd/submatrix.py)
     "dbcsr_amd_bcsr_submatrix_gather", "dbcsr_amd_bcsr_submatrix_scatter",
+    # element-wise operations on two patterns
+    "dbcsr_amd_bcsr_hadamard_count", "dbcsr_amd_bcsr_hadamard_apply", "dbcsr_amd_bcsr_copy_onto", "dbcsr_amd_bcsr_function_of_elements",
 ]
 
 # `kind` of a matrix with symmetry in the C ABI (include/dbcsr_amd_mm.h): bit 0 negates the twin block, bit 1 conjugates it
@@ -228,6 +230,10 @@ def load_library(lab=False):
     L.dbcsr_amd_bcsr_from_dense_count.argtypes = [vp, i32, vp, i64, i64, i64, i32, vp, vp, i32, i32, C.c_double, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), vp]
     L.dbcsr_amd_bcsr_submatrix_gather.argtypes = [vp, i32, BP, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, i64, i64, i64, C.c_double, vp]
     L.dbcsr_amd_bcsr_submatrix_scatter.argtypes = [vp, i32, vp, i64, i64, i64, i32, vp, vp, vp, vp, vp, BP, vp]
+    L.dbcsr_amd_bcsr_hadamard_count.argtypes = [vp, BP, BP, i32, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32), vp]
+    L.dbcsr_amd_bcsr_hadamard_apply.argtypes = [vp, i32, BP, BP, Z, BP, vp]
+    L.dbcsr_amd_bcsr_copy_onto.argtypes = [vp, i32, BP, BP, vp]
+    L.dbcsr_amd_bcsr_function_of_elements.argtypes = [vp, i32, BP, i32, C.c_double, C.c_double, vp]
     if lab:   # diagnostics of the experimental dataflows (dbcsr_amd/csrc/mm_lab_api.h): the shipping build does not export them
         L.dbcsr_amd_mm_tile_stats.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
         L.dbcsr_amd_mm_band_stats.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]

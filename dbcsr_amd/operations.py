@@ -21,6 +21,9 @@
     dbcsr_to_dense(matrix, out)                                 the full matrix as a dense device tensor (dbcsr_to_dense_local / copy_dbcsr_to_fm)
     dbcsr_from_dense(dense, matrix)                             the stored blocks <- the dense tensor's elements (copy_fm_to_dbcsr, keep_sparsity)
     dbcsr_create_from_dense(dense, row_blk_size, col_blk_size, eps)  a new matrix of the blocks of a dense tensor that the block filter keeps
+    dbcsr_hadamard_product(matrix_a, matrix_b, matrix_c, b_assume_value)  C <- A o B on the blocks both store (or on A's, B's missing blocks assumed)
+    dbcsr_copy(matrix_b, matrix_a, keep_sparsity)               B <- A; keep_sparsity: A projected onto B's pattern, in place
+    dbcsr_function_of_elements(matrix_a, func, a0, a1)          x <- f(a1*x + a0) in place, func one of dbcsr_func_*                 (real data)
 
 Same argument names and error behaviour; the work is done by the C-ABI engine (include/dbcsr_amd_mm.h, "Matrix algebra between
 multiplies") on the GPU, for float64, float32 and complex128 data.  One rank / one device here: of a distributed matrix trace, dot
@@ -856,3 +859,145 @@ def dbcsr_create_from_dense(dense, row_blk_size, col_blk_size, eps=0.0, name="",
     if rc != 0:
         raise RuntimeError("dbcsr_amd_bcsr_from_dense_apply failed (%d)" % rc)
     return M
+
+
+# ---- element-wise operations on two patterns ------------------------------------------------------------------------------------------------------------
+# func of dbcsr_function_of_elements (the reference's constants; 5, 6 and 14 are inverse_special, spread_from_zero and truncate: not offered)
+dbcsr_func_inverse = 0
+dbcsr_func_tanh = 1
+dbcsr_func_dtanh = 2
+dbcsr_func_ddtanh = 3
+dbcsr_func_artanh = 4
+dbcsr_func_sin = 7
+dbcsr_func_dsin = 8
+dbcsr_func_ddsin = 9
+dbcsr_func_asin = 10
+dbcsr_func_cos = 11
+dbcsr_func_dcos = 12
+dbcsr_func_ddcos = 13
+_FUNCTIONS = (dbcsr_func_inverse, dbcsr_func_tanh, dbcsr_func_dtanh, dbcsr_func_ddtanh, dbcsr_func_artanh, dbcsr_func_sin, dbcsr_func_dsin,
+              dbcsr_func_ddsin, dbcsr_func_asin, dbcsr_func_cos, dbcsr_func_dcos, dbcsr_func_ddcos)
+
+
+def _check_like(name, what, m, like):
+    """m can take a result with like's sizes, data type and symmetry"""
+    if m.dtype != like.dtype:
+        raise TypeError("%s: the data type of %s differs" % (name, what))
+    s, t = _check_symmetry(name, m), _check_symmetry(name, like)
+    if s != t:
+        raise ValueError("%s: %s has another symmetry (%r, %r)" % (name, what, s, t))
+    if not _same_sizes(m, like):
+        raise ValueError("%s: row or column block sizes of %s differ" % (name, what))
+
+
+def _has_index_of(c, a):
+    """c's index arrays are a's, or hold the same numbers (compared on the device: synchronises)"""
+    if c.row_p is a.row_p and c.col_i is a.col_i and c.blk_p is a.blk_p:
+        return True
+    return c.nblks == a.nblks and torch.equal(c.row_p, a.row_p) and torch.equal(c.col_i, a.col_i) and torch.equal(c.blk_p, a.blk_p)
+
+
+def dbcsr_hadamard_product(matrix_a, matrix_b, matrix_c, b_assume_value=None, engine=None, stream=None):
+    """C <- A o B, element by element (dbcsr_hadamard_product).  The result has the blocks that both A and B store, in A's order, packed;
+    with b_assume_value given it has every block of A, and a block B lacks counts as filled with that value (a value of exactly 1 copies
+    A's block bit for bit).  What matrix_c held before is replaced: it adopts the result, as a multiply hands over C.  The reference's
+    source could not be consulted for the pattern of the result: this is the semantics of this library.  float64, float32 (one
+    multiplication per element: a*b in the data's precision, bit for bit) and complex128; symmetry 'N', and 'S' / 'H' on the stored
+    triangles (the element-wise product of two symmetric or hermitian matrices is one again; 'A' / 'K' change class: ValueError).
+    matrix_c may be matrix_a or matrix_b.  When B has A's index (row_p, col_i, blk_p) and A is packed -- the usual case inside an
+    iteration -- the product is one flat pass, and a matrix_c that is A or B or already has that index is written in place: no index
+    array is written, its index_stamp() stays and a multiply with it still reuses its plan.  Returns True when the flat pass was taken,
+    False otherwise.  Two patterns cost one synchronisation (the size of the result); the engine's saved plan survives either way."""
+    fn = "dbcsr_hadamard_product"
+    sym = _check_pair(fn, matrix_a, matrix_b)
+    if sym in ("A", "K"):
+        raise ValueError("%s: the product of two matrices of symmetry %r is not one of them" % (fn, sym))
+    _check_like(fn, "matrix_c", matrix_c, matrix_a)
+    if b_assume_value is not None:
+        _check_scalar(fn, matrix_a, b_assume_value)
+    code = matrix_a.dtype_code
+    E = engine or default_engine()
+    st = StreamHandle(stream)
+    A, B = matrix_a, matrix_b
+    dev = A.row_p.device
+    a, b = A.desc(), B.desc()
+    on_stream = lambda: torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream())
+    with on_stream():
+        row_p = torch.empty(A.nblkrows + 1, dtype=torch.int32, device=dev)
+    nb, nz, same = C.c_int64(), C.c_int64(), C.c_int32()
+    rc = E.L.dbcsr_amd_bcsr_hadamard_count(E.h, C.byref(a), C.byref(b), 0 if b_assume_value is None else 1, row_p.data_ptr(), C.byref(nb),
+                                           C.byref(nz), C.byref(same), st.ptr)
+    if rc != 0:
+        raise RuntimeError("dbcsr_amd_bcsr_hadamard_count failed (%d)" % rc)
+    value = None if b_assume_value is None else _z(b_assume_value)
+    in_place = bool(same.value) and (matrix_c is A or matrix_c is B or _has_index_of(matrix_c, A))
+    if in_place:
+        # A's own index with C's data area: only that area is written (C.desc(out=True) would bump the stamp)
+        dst = A.desc()
+        dst.data = matrix_c.data.data_ptr() if matrix_c.data.numel() else None
+        out = None
+    else:
+        with on_stream():
+            out = DbcsrMatrix(A.row_blk_size, A.col_blk_size, row_p, torch.empty(nb.value, dtype=torch.int32, device=dev),
+                              torch.empty(nb.value, dtype=torch.int64, device=dev), torch.empty(nz.value, dtype=A.dtype, device=dev), matrix_c.name)
+        dst = out.desc(out=True)
+    rc = E.L.dbcsr_amd_bcsr_hadamard_apply(E.h, code, C.byref(a), C.byref(b), value, C.byref(dst), st.ptr)
+    if rc != 0:
+        raise RuntimeError("dbcsr_amd_bcsr_hadamard_apply failed (%d)" % rc)
+    if out is not None:
+        matrix_c.adopt(out)   # as a multiply hands its result to matrix_c
+    return bool(same.value)
+
+
+def dbcsr_copy(matrix_b, matrix_a, keep_sparsity=False, engine=None, stream=None):
+    """B <- A (dbcsr_copy).  Without keep_sparsity B adopts a copy of A, index and data, and takes A's symmetry.  With
+    keep_sparsity=True B keeps its pattern: every block B stores takes A's block bit for bit where A stores it and becomes +0.0 where A
+    does not -- A projected onto B's pattern.  Only B's data area is written, in place: no index array is written, index_stamp() stays, holes
+    of a B that is not packed keep their bits.  No count step and no synchronisation: asynchronous on stream.  float64, float32 and
+    complex128; same sizes, data type and symmetry (TypeError / ValueError); matrices that share a data area: ValueError."""
+    fn = "dbcsr_copy"
+    _check_symmetry(fn, matrix_a)
+    code = matrix_a.dtype_code
+    if not keep_sparsity:
+        if matrix_b.dtype != matrix_a.dtype:
+            raise TypeError("%s: the data types of the two matrices differ" % fn)
+        if not _same_sizes(matrix_b, matrix_a):
+            raise ValueError("%s: row or column block sizes of the two matrices differ" % fn)
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            matrix_b.adopt(matrix_a.copy())
+        matrix_b.symmetry = matrix_a.symmetry
+        return
+    _check_like(fn, "matrix_b", matrix_b, matrix_a)
+    if matrix_b is matrix_a or _data_overlap(matrix_a.data, matrix_b.data):
+        raise ValueError("%s: the two matrices share a data area" % fn)
+    E = engine or default_engine()
+    st = StreamHandle(stream)
+    a, b = matrix_a.desc(), matrix_b.desc()   # (only B's data area is written)
+    rc = E.L.dbcsr_amd_bcsr_copy_onto(E.h, code, C.byref(a), C.byref(b), st.ptr)
+    if rc != 0:
+        raise RuntimeError("dbcsr_amd_bcsr_copy_onto failed (%d)" % rc)
+
+
+def dbcsr_function_of_elements(matrix_a, func, a0=0.0, a1=1.0, a2=None, engine=None, stream=None):
+    """x <- f(a1*x + a0) in place on every element the index names (dbcsr_function_of_elements); holes keep their bits, the index and
+    index_stamp() stay.  With y = a1*x + a0, func is one of dbcsr_func_inverse 1/y, _tanh tanh y, _dtanh a1*(1 - tanh^2 y), _ddtanh
+    -2*a1^2*tanh y*(1 - tanh^2 y), _artanh atanh y, _sin sin y, _dsin a1*cos y, _ddsin -a1^2*sin y, _asin asin y, _cos cos y, _dcos
+    -a1*sin y, _ddcos -a1^2*cos y.  The reference has three functions more (inverse_special, spread_from_zero, truncate) and a parameter
+    a2; their definitions could not be checked against its sources, so they are not offered rather than guessed: any other func, or an
+    a2 that is not None / 0, raises NotImplementedError.  float64 and float32 (the value is formed in double and rounded once); complex
+    data: NotImplementedError.  Asynchronous on stream."""
+    fn = "dbcsr_function_of_elements"
+    _check_symmetry(fn, matrix_a)
+    if isinstance(func, bool) or not isinstance(func, int) or func not in _FUNCTIONS:
+        raise NotImplementedError("%s: func %r" % (fn, func))
+    if a2 is not None and a2 != 0:
+        raise NotImplementedError("%s: a2 = %r (no function offered here takes a third parameter)" % (fn, a2))
+    code = matrix_a.dtype_code
+    if matrix_a.dtype.is_complex:
+        raise NotImplementedError("%s: complex data" % fn)
+    E = engine or default_engine()
+    st = StreamHandle(stream)
+    d = matrix_a.desc()   # (only the data area is written)
+    rc = E.L.dbcsr_amd_bcsr_function_of_elements(E.h, code, C.byref(d), int(func), float(a0), float(a1), st.ptr)
+    if rc != 0:
+        raise RuntimeError("dbcsr_amd_bcsr_function_of_elements failed (%d)" % rc)

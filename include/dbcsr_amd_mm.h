@@ -551,6 +551,45 @@ int dbcsr_amd_bcsr_submatrix_scatter(void* handle, libsmm_acc_data_t datatype, c
   const int32_t* set_ptr, const int32_t* set_idx, const int32_t* set_off, const int32_t* owner, const int32_t* sub_slot, dbcsr_amd_bcsr* m,
   void* stream);
 
+/* Element-wise operations on two patterns (src/ops/dbcsr_operations.F: dbcsr_hadamard_product, dbcsr_copy with keep_sparsity,
+ * dbcsr_function_of_elements), for the types of the algebra above (any other type code: -10; the functions: real types only).  Every operation goes by the
+ * index, never by the extent of a data area, and relies on ascending block columns per block row as the algebra does: the partner of a block in the
+ * other matrix is found by a binary search of that matrix' row.  NULL arguments and matrices whose nblkrows / nblkcols differ: -1.  They use buffers of
+ * their own: the work areas of the symbolic phase are not touched and a saved plan stays, for two patterns as well.
+ *
+ * dbcsr_hadamard_product: C <- A o B, element by element.  The result has the blocks BOTH operands store, in A's order, packed; with b_assumed / b_value
+ * it has every block of A, and a block B lacks counts as filled with b_value (a b_value of exactly 1 copies A's block bit for bit).  Real data: one
+ * multiplication per element, a * b in the data's precision bit for bit; complex data: re = ar br - ai bi, im = ar bi + ai br in double.  Matrices with
+ * symmetry are multiplied on their stored triangles as they are (the caller checks that the product keeps the symmetry class).  The reference's source
+ * could not be consulted for the pattern of the result: this is the semantics of this library.  Two steps, as the add:
+ *   _hadamard_count  writes dst_row_p [nblkrows + 1] (device) and the block / element counts of the result (host; synchronises).  *same_pattern = 1: A and
+ *     B have the same row_p, col_i AND blk_p and A is packed (the add's check).  b_assumed != 0: the _apply will be given a b_value.
+ *   _hadamard_apply  fills dst (dst->row_p = that row_p; col_i, blk_p [nblks], data [nze] allocated by the caller).  b_value NULL: the intersection; it must
+ *     be given exactly when _count was told b_assumed.  When _count reported same_pattern, dst may be a or b itself: one flat pass over the data area in
+ *     place, no index array is written; a dst with index arrays of its own receives copies of a's.  Otherwise a dst whose data area is a's or b's is
+ *     refused (-1).  One _apply per _count: an _apply without a pending _count, or with operands whose block counts differ from the counted ones, is
+ *     refused (-1) and writes nothing.  What is pending lives in fields and buffers of its own: an add, a norm or a multiply between the two halves does
+ *     not disturb it and is not disturbed by it.  Asynchronous on stream. */
+int dbcsr_amd_bcsr_hadamard_count(void* handle, const dbcsr_amd_bcsr* a, const dbcsr_amd_bcsr* b, int b_assumed, int32_t* dst_row_p, int64_t* nblks,
+  int64_t* nze, int* same_pattern, void* stream);
+int dbcsr_amd_bcsr_hadamard_apply(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* a, const dbcsr_amd_bcsr* b,
+  const double b_value[2] /* NULL: intersection */, dbcsr_amd_bcsr* dst, void* stream);
+/* dbcsr_copy with keep_sparsity: every block the index of dst names <- src's block (r, c) bit for bit, +0.0 in every element where src stores no such
+ * block.  Only dst's data area is written, and of it only the elements its index names: the holes of an unpacked dst and every index array keep their
+ * bits.  No count step, nothing synchronises: asynchronous on stream.  The blocks of src and dst must not overlap (the caller's
+ * contract). */
+int dbcsr_amd_bcsr_copy_onto(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, dbcsr_amd_bcsr* dst, void* stream);
+/* dbcsr_function_of_elements: in place, x <- f(a1 * x + a0) on every element the index of m names (holes keep their bits), formed in double and rounded
+ * once for real_4.  With y = a1 * x + a0: _inverse 1 / y, _tanh tanh y, _dtanh a1 (1 - tanh^2 y), _ddtanh -2 a1^2 tanh y (1 - tanh^2 y), _artanh atanh y,
+ * _sin sin y, _dsin a1 cos y, _ddsin -a1^2 sin y, _asin asin y, _cos cos y, _dcos -a1 sin y, _ddcos -a1^2 cos y.  The reference has three functions more
+ * (inverse_special, spread_from_zero, truncate: codes 5, 6, 14) and a third parameter; their definitions could not be checked and are not guessed: any
+ * other func is refused (-1).  Complex types: -10.  Asynchronous on stream. */
+enum {
+  dbcsr_func_inverse = 0, dbcsr_func_tanh = 1, dbcsr_func_dtanh = 2, dbcsr_func_ddtanh = 3, dbcsr_func_artanh = 4, dbcsr_func_sin = 7,
+  dbcsr_func_dsin = 8, dbcsr_func_ddsin = 9, dbcsr_func_asin = 10, dbcsr_func_cos = 11, dbcsr_func_dcos = 12, dbcsr_func_ddcos = 13
+};
+int dbcsr_amd_bcsr_function_of_elements(void* handle, libsmm_acc_data_t datatype, dbcsr_amd_bcsr* m, int func, double a0, double a1, void* stream);
+
 /* Measurement helper (bench.py, roofline.fabric): what the L2 <-> Infinity-Cache fabric of the current device delivers, in TB/s -- a
  * plain streaming read of a 160 MB window by all CUs, and the block gather of the block-product dataflow (4232-byte blocks from
  * pseudo-random places of the window into LDS, whole 128-byte lines counted).  Takes well under a second; synchronises the device. */

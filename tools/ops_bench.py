@@ -89,6 +89,15 @@ its spread are the result:
 
     python tools/ops_bench.py --submatrix --alternations 7 --warmup 2 --out profiles/submatrix.txt
 
+With --elementwise only the element-wise operations on two patterns are timed (dbcsr_hadamard_product, dbcsr_copy with keep_sparsity,
+dbcsr_function_of_elements; kernels of dbcsr_amd/csrc/mm_elementwise.h), alternating with their yardsticks: had.flat (the whole in-place call on the same
+pattern: index comparison, one synchronisation, elementwise_mul_flat) against the flat dbcsr_add and torch.mul on the data areas; had.general
+(dbcsr_amd_bcsr_hadamard_count + _apply at 50 % overlap, dst allocated once; had.count: the count with its synchronisation alone) against the union add
+of the same pair (general / count of the standard report); copy_onto (B onto A's equal pattern) against A.data.copy_(B.data); function (tanh, in
+place) against torch.tanh_ on the data area.  No condition: times, ratios and their spread are the result:
+
+    python tools/ops_bench.py --elementwise --alternations 7 --warmup 2 --out profiles/elementwise.txt
+
 A sample is `--reps` calls back to back between two device events, divided by reps.  Bytes are counted from the shapes: 8 * (elements read + elements
 written) of the data areas, index arrays left out.  Spread = (max - min) / median over the samples."""
 import argparse
@@ -106,6 +115,7 @@ from dbcsr_amd.matrix import DbcsrMatrix, StreamHandle  # noqa: E402
 from dbcsr_amd.multiply import MultiplyEngine, dbcsr_multiply  # noqa: E402
 from dbcsr_amd.operations import dbcsr_add, dbcsr_get_block_diag, dbcsr_invert_block_diag, dbcsr_scale, dbcsr_scale_by_block_diag  # noqa: E402
 from dbcsr_amd.operations import dbcsr_create_from_dense, dbcsr_from_dense, dbcsr_to_dense  # noqa: E402
+from dbcsr_amd.operations import dbcsr_func_tanh, dbcsr_hadamard_product  # noqa: E402
 from dbcsr_amd.submatrix import dbcsr_submatrix_gather, dbcsr_submatrix_plan, dbcsr_submatrix_scatter  # noqa: E402
 
 
@@ -650,6 +660,118 @@ def submatrix(args, say, lines, rng):
             f.write("\n".join(lines) + "\n")
 
 
+def elementwise(args, say, lines, rng, b, nb, st):
+    E = MultiplyEngine()
+    f64 = L.dbcsr_type_real_8
+    mask = rng.random((nb, nb)) < args.fill_flat
+    A, B = matrix_of(mask, b, 1), matrix_of(mask, b, 2)
+    a, b_ = A.desc(), B.desc()
+    # the general pair of the standard report: three disjoint random sets of blocks S, SA, SB of equal size; A = S + SA, B = S + SB
+    u = rng.random((nb, nb))
+    q = args.fill_general / 2
+    GA, GB = matrix_of((u < 2 * q), b, 3), matrix_of((u < q) | ((u >= 2 * q) & (u < 3 * q)), b, 4)
+    ga, gb = GA.desc(), GB.desc()
+    check = lambda rc: rc == 0 or sys.exit("a library call failed (%d)" % rc)
+    one, beta = (C.c_double * 2)(1.0, 0.0), (C.c_double * 2)(1e-3, 0.0)
+    nblk, nze, same = C.c_int64(), C.c_int64(), C.c_int32()
+
+    def counted(entry, flag):
+        row_p = torch.empty(nb + 1, dtype=torch.int32, device="cuda")
+        count = lambda: check(entry(E.h, C.byref(ga), C.byref(gb), flag, row_p.data_ptr(), C.byref(nblk), C.byref(nze), C.byref(same), st.ptr))
+        count()
+        assert same.value == 0
+        D = DbcsrMatrix(GA.row_blk_size, GA.col_blk_size, row_p, torch.empty(nblk.value, dtype=torch.int32, device="cuda"),
+                        torch.empty(nblk.value, dtype=torch.int64, device="cuda"), torch.empty(nze.value, dtype=torch.float64, device="cuda"))
+        return count, D, D.desc(out=True)
+
+    had_count, HD, hd = counted(E.L.dbcsr_amd_bcsr_hadamard_count, 0)
+    add_count, AD, ad = counted(E.L.dbcsr_amd_bcsr_add_count, 0)
+
+    def had_general():
+        had_count()
+        check(E.L.dbcsr_amd_bcsr_hadamard_apply(E.h, f64, C.byref(ga), C.byref(gb), None, C.byref(hd), st.ptr))
+
+    def add_general():
+        add_count()
+        check(E.L.dbcsr_amd_bcsr_add_apply(E.h, f64, one, C.byref(ga), beta, C.byref(gb), C.byref(ad), st.ptr))
+
+    def had_flat():
+        assert dbcsr_hadamard_product(A, B, A, engine=E) is True
+
+    def add_flat():
+        assert dbcsr_add(A, B, 1.0, 1e-3, engine=E) is True
+
+    # what is timed is right: the first blocks of each result against torch (the whole comparison is the tests' business)
+    head = 4096 * b * b
+    keep = A.data[:head].clone()
+    had_flat()
+    had_general()
+    torch.cuda.synchronize()
+    if not torch.equal(A.data[:head], keep * B.data[:head]):
+        sys.exit("the flat hadamard product is wrong: nothing is timed")
+    shared = torch.as_tensor(np.flatnonzero((u < q)[u < 2 * q])[:64]).cuda()    # positions in GA of blocks both have ...
+    theirs = torch.as_tensor(np.flatnonzero((u < q)[(u < q) | ((u >= 2 * q) & (u < 3 * q))])[:64]).cuda()   # ... and in GB, in the same order
+    want = GA.data.view(-1, b * b)[shared] * GB.data.view(-1, b * b)[theirs]
+    if HD.nblks != int(np.count_nonzero(u < q)) or not torch.equal(HD.data.view(-1, b * b)[:64], want):
+        sys.exit("the general hadamard product is wrong: nothing is timed")
+    check(E.L.dbcsr_amd_bcsr_copy_onto(E.h, f64, C.byref(b_), C.byref(a), st.ptr))
+    if not torch.equal(A.data[:head], B.data[:head]):
+        sys.exit("copy_onto is wrong: nothing is timed")
+    keep = A.data[:head].clone()
+    check(E.L.dbcsr_amd_bcsr_function_of_elements(E.h, f64, C.byref(a), dbcsr_func_tanh, 0.0, 1.0, st.ptr))
+    if not float((A.data[:head] - torch.tanh(keep)).abs().max()) < 1e-15:
+        sys.exit("function_of_elements is wrong: nothing is timed")
+    del keep, want
+    run = {
+        "had.flat": had_flat,
+        "add.flat": add_flat,
+        "torch.mul": lambda: torch.mul(A.data, B.data, out=A.data),
+        "had.general": had_general,
+        "had.count": had_count,
+        "add.general": add_general,
+        "add.count": add_count,
+        "copy_onto": lambda: check(E.L.dbcsr_amd_bcsr_copy_onto(E.h, f64, C.byref(b_), C.byref(a), st.ptr)),
+        "torch.copy_": lambda: A.data.copy_(B.data),
+        "function": lambda: check(E.L.dbcsr_amd_bcsr_function_of_elements(E.h, f64, C.byref(a), dbcsr_func_tanh, 0.0, 1.0, st.ptr)),
+        "torch.tanh_": lambda: A.data.tanh_(),
+    }
+    nbytes = {"had.flat": 24 * A.nze, "add.flat": 24 * A.nze, "torch.mul": 24 * A.nze, "had.general": 8 * 3 * HD.nze, "had.count": 0,
+              "add.general": 8 * (GA.nze + GB.nze + AD.nze), "add.count": 0, "copy_onto": 16 * A.nze, "torch.copy_": 16 * A.nze, "function": 16 * A.nze,
+              "torch.tanh_": 16 * A.nze}
+    times = {k: [] for k in run}
+    for step in range(args.warmup + args.alternations):
+        for k in run:
+            if k in ("copy_onto", "function"):
+                A.data.copy_(B.data)   # (values of the usual size for what follows: the products before shrank them)
+            t = sample(run[k], args.reps)
+            if step >= args.warmup:
+                times[k].append(t)
+    say("")
+    say("same pattern: %d blocks, %.1f MB per matrix; general: %d and %d blocks (%.1f MB each), %d shared (%.1f MB): the product; %d in the union (%.1f MB): the sum"
+        % (A.nblks, 8e-6 * A.nze, GA.nblks, GB.nblks, 8e-6 * GA.nze, HD.nblks, 8e-6 * HD.nze, AD.nblks, 8e-6 * AD.nze))
+    med = {}
+    for k in run:
+        v = sorted(times[k])
+        med[k] = v[len(v) // 2]
+        rate = ("%8.1f GB/s" % (1e-6 * nbytes[k] / med[k])) if nbytes[k] else "   (no data moved)"
+        say("  %-12s  median %8.4f ms  min %8.4f  max %8.4f  spread %5.1f %%  %s   samples: %s"
+            % (k, med[k], v[0], v[-1], 100 * (v[-1] - v[0]) / med[k], rate, " ".join("%.4f" % x for x in times[k])))
+    say("  (GB/s of had.general: the shared blocks read from both operands and written once; the blocks only one operand has are not touched)")
+    say("")
+    say("time against the yardstick of the same run (median / median; the ratio per alternation, sample by sample)")
+    for k, y in (("had.flat", "add.flat"), ("had.flat", "torch.mul"), ("had.general", "add.general"), ("had.count", "add.count"), ("copy_onto", "torch.copy_"),
+                 ("function", "torch.tanh_")):
+        r = sorted(x / z for x, z in zip(times[k], times[y]))
+        say("  %-12s / %-12s  %.2f   (per alternation %.2f ... %.2f)" % (k, y, med[k] / med[y], r[0], r[-1]))
+    had_apply, add_apply = med["had.general"] - med["had.count"], med["add.general"] - med["add.count"]
+    say("  apply = general - count: hadamard %.4f ms (%.1f GB/s), add %.4f ms (%.1f GB/s); per byte moved the hadamard apply runs at %.2f of the add's rate"
+        % (had_apply, 1e-6 * nbytes["had.general"] / had_apply, add_apply, 1e-6 * nbytes["add.general"] / add_apply,
+           (nbytes["had.general"] / had_apply) / (nbytes["add.general"] / add_apply)))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=32768)
@@ -667,6 +789,7 @@ def main():
     ap.add_argument("--block-scale", action="store_true", help="only the block diagonal applied to a matrix: left, right, both, dbcsr_scale and the multiply it replaces")
     ap.add_argument("--dense", action="store_true", help="only the dense conversion: to_dense, from_dense, create_from_dense and what they replace")
     ap.add_argument("--submatrix", action="store_true", help="only the submatrix method: gather, scatter, and the full-set gather against to_dense")
+    ap.add_argument("--elementwise", action="store_true", help="only the element-wise operations on two patterns and their yardsticks")
     ap.add_argument("--mfma-tflops", type=float, default=None, help="with --rank-update / --block-scale: the fp64 MFMA figure bench.py --full measured in the same session")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     args = ap.parse_args()
@@ -693,6 +816,8 @@ def main():
         return dense_conversion(args, say, lines, rng)
     if args.submatrix:
         return submatrix(args, say, lines, rng)
+    if args.elementwise:
+        return elementwise(args, say, lines, rng, b, nb, st)
     only =("norm", "norm.T", "matvec.N", "matvec.T", "matvec.S", "gersh.N", "colnorm", "gersh.S") if args.matvec else None
     # the same-pattern pair
     mask = rng.random((nb, nb)) < args.fill_flat
