@@ -215,13 +215,15 @@ int dbcsr_amd_bcsr_filter_count(void* handle, libsmm_acc_data_t datatype, const 
   *new_nblks = E->host_scalars[0];
   *new_nze = E->host_scalars[1];
   E->flt_new_nblks = E->host_scalars[0];
-  return check(hipGetLastError(), "dbcsr_amd_bcsr_filter_count", __FILE__, __LINE__);
+  const int rc = check(hipGetLastError(), "dbcsr_amd_bcsr_filter_count", __FILE__, __LINE__);
+  E->flt_pending = rc == 0;   // (until the next engine_takes_work_areas: a crop count sets flt_nblks for its own apply half, never this)
+  return rc;
 }
 
 int dbcsr_amd_bcsr_filter_apply(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, dbcsr_amd_bcsr* dst, void* stream) {
   Engine* E = static_cast<Engine*>(handle);
   if (E) plan_invalidate(E);  // this call uses (or changes what feeds) the engine's work areas: the next multiply runs its own symbolic phase
-  if (!E || !src || !dst || E->flt_nblks != src->nblks) return -1;
+  if (!E || !src || !dst || !E->flt_pending || E->flt_new_nblks < 0 || E->flt_nblks != src->nblks) return -1;
   engine_writes_values(E);
   hipStream_t st = stream_of(stream);
   const int nbr = src->nblkrows;
@@ -247,7 +249,7 @@ int dbcsr_amd_bcsr_filter_apply(void* handle, libsmm_acc_data_t datatype, const 
 int dbcsr_amd_bcsr_filter_apply_index(void* handle, const dbcsr_amd_bcsr* src, dbcsr_amd_bcsr* dst, void* stream) {
   Engine* E = static_cast<Engine*>(handle);
   if (E) plan_invalidate(E);  // this call uses (or changes what feeds) the engine's work areas: the next multiply runs its own symbolic phase
-  if (!E || !src || !dst || E->flt_new_nblks < 0 || E->flt_nblks != src->nblks || dst->data != src->data) return -1;
+  if (!E || !src || !dst || !E->flt_pending || E->flt_new_nblks < 0 || E->flt_nblks != src->nblks || dst->data != src->data) return -1;
   hipStream_t st = stream_of(stream);
   if (src->nblkrows == 0 || src->nblks == 0 || E->flt_new_nblks == 0) return 0;
   if (!dst->col_i || !dst->blk_p) return -1;
@@ -395,9 +397,12 @@ int dbcsr_amd_bcsr_twin_count(void* handle, const dbcsr_amd_bcsr* src, int mode,
   hipStream_t st = stream_of(stream);
   const int nbr = src->nblkrows, W = (nbr + 31) / 32;
   E->valid = false;  // shares workspace with the symbolic phase
-  engine_takes_work_areas(E);
+  engine_takes_work_areas(E);   // (ends every pending count, an earlier twin count included; this one is recorded where it has succeeded)
   *nblks = *nze = 0;
-  if (nbr == 0) return 0;
+  if (nbr == 0) {
+    E->twin_mode = mode, E->twin_nblkrows = 0, E->twin_nblks = src->nblks;
+    return 0;
+  }
   if (E->c_bm.ensure((size_t)nbr * W + 1) || E->c_pre.ensure((size_t)nbr * W + 1) || E->row_nnz.ensure((size_t)nbr + 1) ||
       E->blk_nze.ensure(2 * (size_t)src->nblks + 1) || E->c_blk_p_ws.ensure(2 * (size_t)src->nblks + 1) || E->dev_scalars.ensure(16))
     return -1;
@@ -416,7 +421,9 @@ int dbcsr_amd_bcsr_twin_count(void* handle, const dbcsr_amd_bcsr* src, int mode,
   ACC_CHECK(hipMemcpyAsync(E->host_scalars, dsc, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
   ACC_CHECK(hipStreamSynchronize(st));
   *nze = E->host_scalars[1];
-  return check(hipGetLastError(), "dbcsr_amd_bcsr_twin_count", __FILE__, __LINE__);
+  const int rc = check(hipGetLastError(), "dbcsr_amd_bcsr_twin_count", __FILE__, __LINE__);
+  if (rc == 0) E->twin_mode = mode, E->twin_nblkrows = nbr, E->twin_nblks = src->nblks;   // c_bm / c_pre / c_blk_p_ws are this count's until someone takes them
+  return rc;
 }
 
 // kind: 0 symmetric, 1 antisymmetric, 2 hermitian, 3 antihermitian (bit 0 negates the twin, bit 1 conjugates it: twin_of, mm_complex.h)
@@ -426,6 +433,9 @@ int dbcsr_amd_bcsr_twin_apply(void* handle, libsmm_acc_data_t datatype, const db
   if (E) plan_invalidate(E);  // this call uses (or changes what feeds) the engine's work areas: the next multiply runs its own symbolic phase
   if (!E || !src || !dst || src->nblkrows != src->nblkcols || mode < 0 || mode > 2 || kind < 0 || kind > 3) return -1;
   if (datatype != dbcsr_type_real_8 && datatype != dbcsr_type_real_4 && datatype != dbcsr_type_complex_8) return -10;
+  // the fill kernels index c_bm / c_pre / c_blk_p_ws as the count of THIS matrix and mode left them: without one (none yet, or ended by whoever took the
+  // work areas since) nothing is launched.  The count stays pending: the apply half may be repeated.
+  if (E->twin_mode != mode || E->twin_nblks != src->nblks || E->twin_nblkrows != src->nblkrows) return -1;
   hipStream_t st = stream_of(stream);
   const int nbr = src->nblkrows, W = (nbr + 31) / 32;
   engine_writes_values(E);

@@ -126,6 +126,10 @@ struct Engine {
   int filter_in_place = 0;     // dbcsr_amd_mm_set_filter_in_place: dbcsr_amd_multiply's final filter rewrites C's index only
   Window crop_win = {0, 0, 0, 0};       // window of the last dbcsr_amd_bcsr_crop_count
   bool crop_pending = false;
+  bool flt_pending = false;    // a dbcsr_amd_bcsr_filter_count succeeded and nothing has taken the work areas since: keep / prod_start / c_blk_p_ws are a filter's
+  // the last dbcsr_amd_bcsr_twin_count that succeeded and still owns c_bm / c_pre / c_blk_p_ws: its mode (-1: none pending) and its matrix
+  int twin_mode = -1, twin_nblkrows = 0;
+  int64_t twin_nblks = 0;
   KPassMemo kpass_memo;  // dbcsr_amd_multiply's k-pass decision for the last stamped A operand (mm_api.hip)
 
   // ---- matrix algebra (mm_engine_algebra.h): buffers of its own, nothing a saved plan depends on.  Only the general (union) add borrows the symbolic
@@ -196,13 +200,18 @@ struct Engine {
 // or another descriptor of the same data area: any write forgets them.)
 static inline void engine_writes_values(Engine* E) { E->norms_data = nullptr; }
 
-// The count halves of the two-call protocols (filter, crop, union add) leave their answer in work areas that the symbolic phase, each other's count, the
-// transpose and the twin moves write too.  Whoever is about to write those areas calls this first: a count that is still pending is over, and its apply
-// half then refuses (-1) and writes nothing instead of compacting by what this call left there.
+// The count halves of the two-call protocols (filter, crop, union add, twin / desymmetrize) leave their answer in work areas that the symbolic phase, each
+// other's count and the transpose write too.  Whoever is about to write those areas calls this first: a count that is still pending is over, and its
+// apply half then refuses (-1) and writes nothing instead of compacting by what this call left there.  Every apply half asks for a pending count of ITS
+// OWN pair (flt_pending, crop_pending, add_mode, twin_mode), never for a block count alone: a crop count of a matrix with as many blocks as the filter's
+// ends the filter's count like any other.  The filter's and the twin's counts stay pending after an apply (the apply may be repeated); a count of a twin
+// is pending for one matrix shape (nblks, nblkrows) and one mode.
 static inline void engine_takes_work_areas(Engine* E) {
   E->flt_nblks = -1;
   E->flt_new_nblks = -1;
+  E->flt_pending = false;
   E->crop_pending = false;
+  E->twin_mode = -1;
   if (E->add_mode == 2) E->add_mode = 0;
 }
 

@@ -234,7 +234,11 @@ int dbcsr_amd_mm_timing(void* handle, float* ms_fill, float* ms_numeric);
  * Operands (the reference desymmetrizes them while it builds the multiplication images, src/mm/dbcsr_mm_cannon.F:284, 351-379): src holds one block per
  * pair (any mix of upper and lower blocks); the full matrix gets block (c, r) = twin(block (r, c)) in addition.  _count writes dst_row_p [nblkrows+1]
  * (device) and the block / element counts (host, synchronises); _apply fills caller-allocated dst arrays (dst->row_p = that row_p), blocks packed in index
- * order.  An operand is desymmetrized BEFORE op() is applied: 'N', 'T' and 'C' all stay meaningful for a hermitian operand. */
+ * order.  An operand is desymmetrized BEFORE op() is applied: 'N', 'T' and 'C' all stay meaningful for a hermitian operand.
+ * _apply: -1 when no count of this matrix and mode is pending (none since the handle was made, or a symbolic phase, a transpose or another pair's count
+ * -- filter, crop, union add -- has run since: they write the areas the count left its answer in), for a src with another nblks / nblkrows than the
+ * counted one, and -- dbcsr_amd_bcsr_twin_apply -- for another mode than the counted one.  A refused _apply launches nothing and writes nothing.  The
+ * count stays pending after an _apply: the same src may be filled again. */
 int dbcsr_amd_bcsr_desymmetrize_count(void* handle, const dbcsr_amd_bcsr* src, int32_t* dst_row_p, int64_t* nblks, int64_t* nze, void* stream);
 int dbcsr_amd_bcsr_desymmetrize_apply(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, int kind, dbcsr_amd_bcsr* dst, void* stream);
 
@@ -253,6 +257,7 @@ int dbcsr_amd_bcsr_desymmetrize_apply(void* handle, libsmm_acc_data_t datatype, 
  * and alpha, beta are real (the caller's contract, as for real data); for other inputs this formula IS what the call computes. */
 /* desymmetrize in one call: dst's arrays are allocated by the library (dbcsr_amd_bcsr_release frees them), size arrays borrowed from src */
 int dbcsr_amd_bcsr_desymmetrized(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, int kind, dbcsr_amd_bcsr* dst, void* stream);
+/* (_twin_apply: -1 when no count of this matrix and mode is pending, as for desymmetrize_apply above) */
 int dbcsr_amd_bcsr_twin_count(void* handle, const dbcsr_amd_bcsr* src, int mode, int32_t* dst_row_p, int64_t* nblks, int64_t* nze, void* stream);
 int dbcsr_amd_bcsr_twin_apply(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, int mode, int kind, dbcsr_amd_bcsr* dst,
   void* stream);

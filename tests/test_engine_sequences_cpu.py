@@ -88,3 +88,38 @@ def test_stale_norms_would_keep_another_set_of_blocks(op):
     print("%s: %d blocks, %d kept before the change, %d after it, %.0f %% change sides" % (op, before.size, before.sum(), after.sum(), 100 * differ))
     assert differ >= 0.10
     assert 0 < after.sum() < after.size
+
+
+# ---- part E: the algebra walks ---------------------------------------------------------------------------------------------------------------------------
+def test_the_algebra_pool_is_what_the_walks_need():
+    hs = [ES.alg(k) for k in range(len(ES.ALG_POOL))]
+    for h in hs:
+        print(h)
+        assert np.array_equal(h.M.row_sizes, h.M.col_sizes) and all(h.M.col_i[h.M.row_p[r]:h.M.row_p[r + 1]].tolist().count(r) == 1 for r in range(h.nb))
+        assert 55 <= h.n <= 600 and h.sizes.max() <= 96, "what the block inverse and the block scale accept"
+        assert 0.3 <= h.M.nblks / h.nb ** 2 <= 0.6 and 0.3 <= h.Q.nblks / h.nb ** 2 <= 0.6
+        assert h.Q.nblks != h.M.nblks or not np.array_equal(h.Q.col_i, h.M.col_i), "Q has another pattern"
+        assert max(h.subs) < h.nb and h.sub_n <= h.n
+    types = [h.dtype.name for h in hs]
+    assert len(hs) == 10 and (types.count("float64"), types.count("float32"), types.count("complex128")) == (5, 3, 2)
+    assert len({h.sizes.tobytes() for h in hs}) > 8, "more sets of block sizes than the engine remembers: its ring wraps"
+
+
+def test_the_algebra_walks_cover_every_operation():
+    assert set(ES.ALG_WALKS) == {"descending", "ascending", "shuffled"} and len(set(ES.ALG_OPS)) == len(ES.ALG_OPS) >= 30
+    preds = {op: set() for op in ES.ALG_OPS}
+    for name, w in ES.ALG_WALKS.items():
+        assert all(op in ES.ALG_OPS and ES.alg(k).admits(op) for op, k in w), name
+        for op in ES.ALG_OPS:
+            assert sum(o == op for o, _ in w) >= 2, (name, op)
+        t = [ES.alg(k).dtype.name for _, k in w]
+        changes = sum(x != y for x, y in zip(t, t[1:]))
+        print("%s: %d steps, the element type changes %d times" % (name, len(w), changes))
+        assert changes >= 10, name
+        for (a, _), (b, _) in zip(w, w[1:]):
+            preds[b].add(a)
+    assert all(len(p) >= 3 for p in preds.values()), {op: sorted(p) for op, p in preds.items() if len(p) < 3}
+    full = lambda name: [ES.alg(k).n for _, k in ES.ALG_WALKS[name]]
+    assert all(x >= y for x, y in zip(full("descending"), full("descending")[1:])) and full("descending")[0] > full("descending")[-1]
+    assert all(x <= y for x, y in zip(full("ascending"), full("ascending")[1:])) and full("ascending")[0] < full("ascending")[-1]
+    assert len({k for _, k in ES.ALG_WALKS["shuffled"]}) >= 8

@@ -10,10 +10,13 @@ A. a multiply does not depend on the engine's past: the walks of tests/engine_se
 B. other users of the engine between two multiplies of the same operands.
 C. the two-call protocols and the announcements, through the C entries.
 D. a shipping and a lab engine alive together.
+E. the algebra against itself: every public operation of operations.py and submatrix.py and the engine's filter, crop, transpose and desymmetrize in
+   three walks on one engine, over ten matrices of three element types and ten sets of block sizes (the pool and the walks: tests/engine_sequences.py).
 
 Host operands, oracle results (functools.lru_cache in tests/engine_sequences.py) and fresh-engine results (the module-scoped `fresh`) are computed once."""
 import contextlib
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -22,6 +25,7 @@ import torch
 
 from dbcsr_amd import lib as L
 from dbcsr_amd import operations as OPS
+from dbcsr_amd import submatrix as SUB
 from dbcsr_amd.cannon import gather_blocks
 from dbcsr_amd.matrix import DbcsrMatrix, StreamHandle
 from dbcsr_amd.multiply import MultiplyEngine, _z, dbcsr_multiply
@@ -168,10 +172,13 @@ def test_shuffled_a_on_a_side_stream(fresh):
 MIX = [1, 13, 1, 23, 1, 32, 1, 7]
 B_CASE = (300, 280, 300, 0.5, 0.5, 0.6, MIX, [1, 23, 1, 5, 1, 32], MIX)    # (A is square with equal row and column block sizes: set_diag applies to it)
 B_ALPHA, B_BETA = 0.7, 1.3
-IN_PLACE = ES.STALE_OPS
-REBUILT = ("filtered", "filtered_in_place", "crop", "transpose", "add_union")
+IN_PLACE = ES.STALE_OPS_FIRST
+REBUILT = ("filtered", "filtered_in_place", "crop", "transpose", "add_union", "desymmetrized", "twin_moved")
 REUSED = ("gather", "add_flat", "scale", "add_on_diag", "trace", "dot", "norm_frobenius", "norm_maxabs", "norm_gershgorin", "norm_column", "gershgorin_norm",
-          "get_diag", "set_diag", "scale_by_vector", "matvec", "multivec", "rank_update")
+          "get_diag", "set_diag", "scale_by_vector", "matvec", "multivec", "rank_update",
+          "get_block_diag", "invert_block_diag", "scale_by_block_diag", "to_dense", "from_dense", "create_from_dense", "submatrix_gather", "submatrix_scatter",
+          "hadamard_flat", "hadamard_two_patterns", "copy_keep_sparsity", "function_of_elements")
+SUBS = [0, 7, 31, 119]   # the submatrices of part B's gather and scatter (of one per block column)
 
 
 class Between:
@@ -189,9 +196,11 @@ class Between:
         self.X = dev_to_bcsr(dX)
         self.Y = O.Bcsr(self.X.row_sizes, self.X.col_sizes, self.X.row_p, self.X.col_i, self.X.blk_p, np.cos(np.arange(self.X.data.size, dtype=np.float64)))
         self.Z = O.make_random_matrix(sizes, sizes, 0.6, O.RANDMAT_SEED_INIT + 92)
+        self.T = ES.triangle(self.X)    # (the stored triangle of X, packed: what the twin moves and desymmetrize take)
         n = int(sizes.sum())
         rng = np.random.default_rng(8)
         self.v, self.V, self.W = rng.uniform(-1, 1, n), rng.uniform(-1, 1, (n, 5)), rng.uniform(-1, 1, (n, 5))
+        self.window = rng.uniform(-1, 1, (n, n))    # (a dense tensor of X's full size)
         norms = np.sort(np.sqrt(FIP.block_sq_norms(self.X)))
         self.eps = float(0.5 * (norms[len(norms) // 2 - 1] + norms[len(norms) // 2]))
         assert self.X.nblks > 10 * self.C.nblks
@@ -254,6 +263,45 @@ class Between:
         elif name == "rank_update":
             OPS.dbcsr_rank_update(X, torch.as_tensor(self.V).cuda(), torch.as_tensor(self.W).cuda(), 0.3, 0.6, engine=eng)
             res = mat(X)
+        elif name in ("desymmetrized", "twin_moved"):
+            T = to_dev(self.T)
+            T.symmetry = "S"
+            res = mat(eng.desymmetrized(T) if name == "desymmetrized" else eng.twin_moved(T, 1, "S"))
+        elif name == "get_block_diag":
+            res = mat(OPS.dbcsr_get_block_diag(X, engine=eng))
+        elif name == "invert_block_diag":     # (X's own diagonal blocks: none above 7)
+            res = OPS.dbcsr_invert_block_diag(X, engine=eng) + mat(X)
+        elif name == "scale_by_block_diag":
+            OPS.dbcsr_scale_by_block_diag(X, OPS.dbcsr_get_block_diag(Y, engine=eng), "both", "T", 0.5, engine=eng)
+            res = mat(X)
+        elif name == "to_dense":
+            res = (OPS.dbcsr_to_dense(X, engine=eng).cpu().numpy(),)
+        elif name == "from_dense":
+            OPS.dbcsr_from_dense(torch.as_tensor(self.window).cuda(), X, engine=eng)
+            res = mat(X)
+        elif name == "create_from_dense":     # (Z's blocks out of its dense form: the blocks Z lacks are zero and are dropped)
+            M = OPS.dbcsr_create_from_dense(torch.as_tensor(self.Z.to_dense()).cuda(), X.row_blk_size, X.col_blk_size, eps=1e-3, engine=eng)
+            assert 0 < M.nblks <= self.Z.nblks
+            res = mat(M)
+        elif name == "submatrix_gather":
+            res = (SUB.dbcsr_submatrix_gather(X, SUB.dbcsr_submatrix_plan(X), subs=SUBS, pad_diag=1.0, engine=eng).cpu().numpy(),)
+        elif name == "submatrix_scatter":     # (Y has X's pattern: its windows onto X)
+            plan = SUB.dbcsr_submatrix_plan(X)
+            SUB.dbcsr_submatrix_scatter(SUB.dbcsr_submatrix_gather(Y, plan, subs=SUBS, engine=eng), X, plan, subs=SUBS, engine=eng)
+            res = mat(X)
+        elif name == "hadamard_flat":
+            assert OPS.dbcsr_hadamard_product(X, Y, X, engine=eng) is True
+            res = mat(X)
+        elif name == "hadamard_two_patterns":
+            assert OPS.dbcsr_hadamard_product(X, to_dev(self.Z), X, engine=eng) is False
+            assert 0 < X.nblks < self.X.nblks
+            res = mat(X)
+        elif name == "copy_keep_sparsity":
+            OPS.dbcsr_copy(X, to_dev(self.Z), keep_sparsity=True, engine=eng)
+            res = mat(X)
+        elif name == "function_of_elements":
+            OPS.dbcsr_function_of_elements(X, OPS.dbcsr_func_tanh, 0.1, 2.0, engine=eng)
+            res = mat(X)
         else:
             raise AssertionError(name)
         torch.cuda.synchronize()
@@ -306,6 +354,24 @@ def apply_in_place(eng, D, op, host):
         OPS.dbcsr_scale_by_vector(D, v[0], "right", engine=eng)
     elif op == "rank_update":
         OPS.dbcsr_rank_update(D, v[0], v[1], 40.0, 0.25, "T", engine=eng)
+    elif op == "add_on_diag":
+        stamp = D.index_stamp()
+        OPS.dbcsr_add_on_diag(D, 10.0, engine=eng)
+        assert D.index_stamp() == stamp, "every diagonal block is stored: values only"
+    elif op == "invert_block_diag":
+        assert OPS.dbcsr_invert_block_diag(D, engine=eng) == (0, -1)
+    elif op == "scale_by_block_diag":
+        OPS.dbcsr_scale_by_block_diag(D, to_dev(ES.stale_operand(op)), "left", engine=eng)
+    elif op == "function_of_elements":
+        OPS.dbcsr_function_of_elements(D, OPS.dbcsr_func_inverse, engine=eng)
+    elif op == "hadamard_in_place":
+        assert OPS.dbcsr_hadamard_product(D, to_dev(ES.stale_operand(op)), D, engine=eng) is True, "the flat pass"
+    elif op == "copy_keep_sparsity":
+        OPS.dbcsr_copy(D, to_dev(ES.stale_operand(op)), keep_sparsity=True, engine=eng)
+    elif op == "from_dense":
+        OPS.dbcsr_from_dense(v[0], D, engine=eng)
+    elif op == "submatrix_scatter":
+        SUB.dbcsr_submatrix_scatter(v[0], D, SUB.dbcsr_submatrix_plan(D), engine=eng)
     else:
         raise AssertionError(op)
 
@@ -501,16 +567,23 @@ def test_norms_do_not_survive_a_new_symbolic_phase():
 # count / apply pairs with another engine call between their halves.  EXPECT is read from the code (csrc/mm_engine_state.h: engine_takes_work_areas): the
 # symbolic phase and every count half take the work areas the pending count left its answer in, so its apply half refuses (-1) and writes nothing; a
 # reduction of the algebra has buffers of its own and the apply half gives the undisturbed pair's result.  The flat add keeps its answer in scalars.
-PAIRS = ("filter", "filter_index", "crop", "add_union", "add_flat")
-DISTURB = ("multiply", "other_count", "reduction")
-EXPECT = {(p, d): ("result" if d == "reduction" or p == "add_flat" else "refuse") for p in PAIRS for d in DISTURB}
+# "desymmetrize" and "twin_canonical" are dbcsr_amd_bcsr_twin_count / _apply with mode 0 and 1 (kind 0) on the stored triangle of X: their count is in c_bm,
+# c_pre and c_blk_p_ws.  "same_size_count" is ANOTHER pair's count on the very matrix of the pending one -- the same block count, the one thing a guard that
+# only compares block counts cannot tell apart; "algebra_scan" runs three entries of the algebra whose exclusive_scan rewrites the scan's partial sums and
+# alg_i32 / alg_i64, none of which a pending count lives in.
+PAIRS = ("filter", "filter_index", "crop", "add_union", "add_flat", "desymmetrize", "twin_canonical")
+TWIN_MODE = {"desymmetrize": 0, "twin_canonical": 1}
+DISTURB = ("multiply", "other_count", "same_size_count", "reduction", "algebra_scan")
+EXPECT = {(p, d): ("result" if d in ("reduction", "algebra_scan") or p == "add_flat" else "refuse") for p in PAIRS for d in DISTURB}
 
 
 class Pair:
     def __init__(self, b, pair, eng, X=None, eps=None):
         self.pair, self.eng, self.sth = pair, eng, StreamHandle(None)
         self.eps = b.eps if eps is None else eps
-        self.X = to_dev(b.X if X is None else X)
+        self.mode = TWIN_MODE.get(pair)
+        self.host = (b.X if self.mode is None else b.T) if X is None else X
+        self.X = to_dev(self.host)
         self.Y = to_dev(b.Z if pair == "add_union" else b.Y)
         self.row_p = torch.full((self.X.nblkrows + 1,), -7, dtype=torch.int32, device="cuda")
         self.nb, self.nz = C.c_int64(), C.c_int64()
@@ -523,6 +596,8 @@ class Pair:
             rc = lib.dbcsr_amd_bcsr_filter_count(h, X.dtype_code, C.byref(src), self.eps, *args, self.sth.ptr)
         elif self.pair == "crop":
             rc = lib.dbcsr_amd_bcsr_crop_count(h, X.dtype_code, C.byref(src), 50, 400, 30, 500, *args, self.sth.ptr)
+        elif self.mode is not None:
+            rc = lib.dbcsr_amd_bcsr_twin_count(h, C.byref(src), self.mode, *args, self.sth.ptr)
         else:
             y, same = self.Y.desc(), C.c_int32()
             rc = lib.dbcsr_amd_bcsr_add_count(h, C.byref(src), C.byref(y), 0, *args, C.byref(same), self.sth.ptr)
@@ -543,6 +618,8 @@ class Pair:
             rc = lib.dbcsr_amd_bcsr_filter_apply_index(h, C.byref(src), C.byref(d), self.sth.ptr)
         elif self.pair == "crop":
             rc = lib.dbcsr_amd_bcsr_crop_apply(h, X.dtype_code, C.byref(src), C.byref(d), self.sth.ptr)
+        elif self.mode is not None:
+            rc = lib.dbcsr_amd_bcsr_twin_apply(h, X.dtype_code, C.byref(src), self.mode, 0, C.byref(d), self.sth.ptr)
         else:
             y = self.Y.desc()
             rc = lib.dbcsr_amd_bcsr_add_apply(h, X.dtype_code, _z(0.5), C.byref(src), _z(2.0), C.byref(y), C.byref(d), self.sth.ptr)
@@ -566,6 +643,15 @@ def test_another_call_between_count_and_apply(pair, disturb, between, long_lived
         same_result(9, run(eng, 9), fresh(9), "between the halves of %s" % pair)
     elif disturb == "other_count":
         Pair(b, "crop" if pair != "crop" else "filter", eng, X=ES.host(16).C, eps=0.5).count()   # (of another matrix, of other sizes)
+    elif disturb == "same_size_count":
+        other = Pair(b, "crop" if pair != "crop" else "filter", eng, X=p.host)   # (of the pending count's own matrix: the same block count)
+        assert other.X.nblks == p.X.nblks
+        other.count()
+    elif disturb == "algebra_scan":
+        h16 = ES.host(16).C
+        D = OPS.dbcsr_get_block_diag(to_dev(b.Z), engine=eng)
+        M = OPS.dbcsr_create_from_dense(torch.as_tensor(h16.to_dense()).cuda(), h16.row_sizes, h16.col_sizes, eps=0.5, engine=eng)
+        assert D.nblks > 0 and 0 < M.nblks <= h16.nblks and OPS.dbcsr_gershgorin_norm(to_dev(b.Y), engine=eng) > 0
     else:
         assert OPS.dbcsr_frobenius_norm(to_dev(ES.host(16).C), engine=eng) > 0 and np.isfinite(OPS.dbcsr_trace(to_dev(b.Y), engine=eng))
     rc, *got = p.apply()
@@ -597,7 +683,20 @@ def test_refusals_leave_the_engine_usable(fresh, between):
         with pytest.raises(exc):
             f(*a, **k)
 
+    T = to_dev(b.T)
+    t = T.desc()
+    t_before = T.data.clone()
+    t_row_p = torch.empty(T.nblkrows + 1, dtype=torch.int32, device="cuda")
+    t_nb, t_nz = C.c_int64(), C.c_int64()
+
+    def twin_with_another_mode():
+        """a count of mode 1 (triangle -> canonical form), then the apply half of mode 0 (desymmetrize): its result would be larger than what was counted"""
+        assert eng.L.dbcsr_amd_bcsr_twin_count(eng.h, C.byref(t), 1, t_row_p.data_ptr(), C.byref(t_nb), C.byref(t_nz), sth.ptr) == 0
+        assert t_nb.value == T.nblks
+        return eng.L.dbcsr_amd_bcsr_twin_apply(eng.h, T.dtype_code, C.byref(t), 0, 0, C.byref(t), sth.ptr) == -1
+
     refusals = [
+        lambda: eng.L.dbcsr_amd_bcsr_twin_apply(eng.h, T.dtype_code, C.byref(t), 0, 0, C.byref(t), sth.ptr) == -1,   # this engine has never counted
         lambda: c_update(eng, X, "T", 1.0, 1.0, 3, x, n, 3, x, n, 3, code=L.dbcsr_type_complex_4) == -10,
         lambda: c_update(eng, X, "T", 1.0, 1.0, 3, None, n, 3, x, n, 3) == -1,
         lambda: c_update(eng, X, "N", 1.0, 1.0, 3, x, n, 3, x, n, 3) == -1,
@@ -612,6 +711,7 @@ def test_refusals_leave_the_engine_usable(fresh, between):
             b.C.row_sizes, b.C.col_sizes, b.C.row_p, b.C.col_i, b.C.blk_p, b.C.data.astype(np.float32))), engine=eng) is None,
         lambda: expect(ValueError, eng.accumulate, 1.0, to_dev(b.A), to_dev(b.B), eng.filtered(to_dev(b.C), float(np.median(np.sqrt(FIP.block_sq_norms(b.C)))),
                                                                                                 in_place=True)) is None,
+        twin_with_another_mode,
     ]
     indices = ES.WALKS["shuffled_b"][:len(refusals)]
     for step, (i, refuse) in enumerate(zip(indices, refusals)):
@@ -620,6 +720,7 @@ def test_refusals_leave_the_engine_usable(fresh, between):
         against_oracle(i, got[0], got[1])
         same_result(i, got, fresh(i), "after refusal %d" % step)
     assert torch.equal(X.data, before), "a refusal wrote the matrix"
+    assert torch.equal(T.data, t_before) and np.array_equal(T.to_host()[3], b.T.col_i), "a refused twin_apply wrote the matrix"
 
 
 # ---- D. two engines in one process ---------------------------------------------------------------------------------------------------------------------------
@@ -631,3 +732,308 @@ def test_a_shipping_and_a_lab_engine_alive_together(fresh):
             got = run(eng, i)
             against_oracle(i, got[0], got[1])
             same_result(i, got, fresh(i, (), is_lab), "%s engine, step %d" % ("lab" if is_lab else "shipping", step))
+
+
+# ---- E. an algebra walk --------------------------------------------------------------------------------------------------------------------------------------
+# tests/engine_sequences.py has the pool, the operations and the walks.  alg_run is one operation on one pool matrix through an engine: what it returned or
+# wrote, as a tuple of numpy arrays and numbers.  alg_check compares such a result with the reference that the operation's own test file uses, at that
+# file's bar (the helpers are imported; this file has no tolerance of its own).  A step of a walk must have the bits of the same operation on a fresh
+# engine; the fresh results are computed and checked once per (operation, matrix).
+from tests import elementwise_ref as R                # noqa: E402
+from tests import submatrix_ref as SR                 # noqa: E402
+from tests import test_gpu_block_inverse as BI        # noqa: E402
+from tests import test_gpu_block_scale as BS          # noqa: E402
+from tests import test_gpu_dense as GD                # noqa: E402
+from tests import test_gpu_elementwise as EW          # noqa: E402
+from tests import test_gpu_matrix_norms as MN         # noqa: E402
+from tests import test_gpu_matrix_ops as MO           # noqa: E402
+from tests import test_gpu_matvec as MV               # noqa: E402
+from tests import test_gpu_multivec as MVV            # noqa: E402
+from tests import test_gpu_rank_update as RU          # noqa: E402
+
+
+def cu(a):
+    return torch.as_tensor(np.ascontiguousarray(a)).cuda()
+
+
+def alg_scalar(h, name):
+    """the scalars of an operation, as its own test file takes them"""
+    cplx = h.dtype.kind == "c"
+    if name in ("add_flat", "add_union"):
+        return MO.scalars(h.dtype)
+    if name == "scale":
+        return MO.scalars(h.dtype)[1]
+    if name == "add_on_diag":
+        return 1.5 - 0.5j if cplx else -1.5
+    if name == "scale_by_block_diag":
+        return BS.alpha_of(h.dtype)
+    return MV.scalars(h.dtype)    # matvec, multivec, rank_update
+
+
+def alg_vectors(h, name):
+    """the dense operands of an operation on the host"""
+    n, dt = h.n, h.dtype
+    if name == "set_diag":
+        return (MN.random_vector(n, dt, 4),)
+    if name == "scale_by_vector":
+        return (MN.random_vector(n, dt, 5),)
+    if name == "matvec":
+        return MN.random_vector(n, dt, 21), MN.random_vector(n, dt, 22)
+    if name == "multivec":
+        return MVV.random_vectors(n, 5, dt, 41), MVV.random_vectors(n, 5, dt, 42)
+    if name == "rank_update":
+        return RU.inputs(h.M, 3)
+    if name == "from_dense":
+        return (np.ascontiguousarray(MN.random_vector(n * n, dt, 9).reshape(n, n)),)
+    if name == "submatrix_scatter":
+        return (np.ascontiguousarray(MN.random_vector(len(h.subs) * h.sub_n ** 2, dt, 11).reshape(len(h.subs), h.sub_n, h.sub_n)),)
+    raise AssertionError(name)
+
+
+def alg_block_diag(h):
+    """the operand of dbcsr_scale_by_block_diag: the diagonal blocks of Q"""
+    return MN.subset(h.Q, lambda r, c: r == c)
+
+
+def alg_run(name, eng, k):
+    h = ES.alg(k)
+    M = to_dev(h.M)
+    mat = lambda D: tuple(D.to_host()[2:])
+    if name in ("add_flat", "add_union"):
+        al, be = alg_scalar(h, name)
+        assert OPS.dbcsr_add(M, to_dev(h.T if name == "add_flat" else h.Q), al, be, engine=eng) is (name == "add_flat")
+        res = mat(M)
+    elif name == "scale":
+        OPS.dbcsr_scale(M, alg_scalar(h, name), engine=eng)
+        res = mat(M)
+    elif name == "add_on_diag":
+        OPS.dbcsr_add_on_diag(M, alg_scalar(h, name), engine=eng)
+        res = mat(M)
+    elif name == "trace":
+        res = (OPS.dbcsr_trace(M, engine=eng),)
+    elif name == "dot":
+        res = (OPS.dbcsr_dot(M, to_dev(h.Q), engine=eng),)
+    elif name == "frobenius_norm":
+        res = (OPS.dbcsr_frobenius_norm(M, engine=eng),)
+    elif name == "maxabs_norm":
+        res = (OPS.dbcsr_maxabs_norm(M, engine=eng),)
+    elif name == "gershgorin_norm":
+        res = (OPS.dbcsr_gershgorin_norm(M, engine=eng),)
+    elif name == "norm_column":
+        res = (OPS.dbcsr_norm(M, OPS.dbcsr_norm_column, engine=eng).cpu().numpy(),)
+    elif name == "get_diag":
+        res = (OPS.dbcsr_get_diag(M, engine=eng).cpu().numpy(),)
+    elif name == "set_diag":
+        OPS.dbcsr_set_diag(M, cu(alg_vectors(h, name)[0]), engine=eng)
+        res = mat(M)
+    elif name == "scale_by_vector":
+        OPS.dbcsr_scale_by_vector(M, cu(alg_vectors(h, name)[0]), "right", engine=eng)
+        res = mat(M)
+    elif name == "matvec":
+        x, y = alg_vectors(h, name)
+        al, be = alg_scalar(h, name)
+        res = (OPS.dbcsr_matvec(M, cu(x), cu(y), al, be, "T", engine=eng).cpu().numpy(),)
+    elif name == "multivec":
+        x, y = alg_vectors(h, name)
+        al, be = alg_scalar(h, name)
+        res = (OPS.dbcsr_multivec(M, cu(x), cu(y), al, be, "N", engine=eng).cpu().numpy(),)
+    elif name == "rank_update":
+        x, y = alg_vectors(h, name)
+        al, be = alg_scalar(h, name)
+        OPS.dbcsr_rank_update(M, cu(x), cu(y), al, be, "T", engine=eng)
+        res = mat(M)
+    elif name == "get_block_diag":
+        res = mat(OPS.dbcsr_get_block_diag(M, engine=eng))
+    elif name == "invert_block_diag":
+        res = OPS.dbcsr_invert_block_diag(M, engine=eng) + mat(M)
+    elif name == "scale_by_block_diag":
+        OPS.dbcsr_scale_by_block_diag(M, to_dev(alg_block_diag(h)), "left", "T", alg_scalar(h, name), engine=eng)
+        res = mat(M)
+    elif name == "to_dense":
+        res = (OPS.dbcsr_to_dense(M, engine=eng).cpu().numpy(),)
+    elif name == "from_dense":
+        OPS.dbcsr_from_dense(cu(alg_vectors(h, name)[0]), M, engine=eng)
+        res = mat(M)
+    elif name == "create_from_dense":
+        res = mat(OPS.dbcsr_create_from_dense(cu(MN.dense(h.Q)), M.row_blk_size, M.col_blk_size, eps=GD.EPS, engine=eng))
+    elif name in ("hadamard_flat", "hadamard_two_patterns"):
+        assert OPS.dbcsr_hadamard_product(M, to_dev(h.T if name == "hadamard_flat" else h.Q), M, engine=eng) is (name == "hadamard_flat")
+        res = mat(M)
+    elif name == "copy_keep_sparsity":
+        OPS.dbcsr_copy(M, to_dev(h.Q), keep_sparsity=True, engine=eng)
+        res = mat(M)
+    elif name == "function_of_elements":
+        F = to_dev(h.F)
+        OPS.dbcsr_function_of_elements(F, EW.FUNCS[ES.ALG_FUNCTION[0]], *ES.ALG_FUNCTION[1:], engine=eng)
+        res = mat(F)
+    elif name == "submatrix_gather":
+        res = (SUB.dbcsr_submatrix_gather(M, SUB.dbcsr_submatrix_plan(M), subs=h.subs, pad_diag=1.0, engine=eng).cpu().numpy(),)
+    elif name == "submatrix_scatter":
+        SUB.dbcsr_submatrix_scatter(cu(alg_vectors(h, name)[0]), M, SUB.dbcsr_submatrix_plan(M), subs=h.subs, engine=eng)
+        res = mat(M)
+    elif name == "submatrix_apply":      # (an exact function, as the submatrix file's own test takes one)
+        res = mat(SUB.dbcsr_submatrix_apply(M, lambda X: X.transpose(-1, -2).contiguous(), plan=SUB.dbcsr_submatrix_plan(M, h.groups), engine=eng))
+    elif name == "filtered":
+        res = mat(eng.filtered(M, h.eps))
+    elif name == "cropped":
+        res = mat(eng.cropped(M, *h.crop))
+    elif name == "transposed":
+        res = mat(eng.transposed(M))
+    elif name == "desymmetrized":
+        T = to_dev(h.tri)
+        T.symmetry = h.symmetry
+        res = mat(eng.desymmetrized(T))
+    else:
+        raise AssertionError(name)
+    torch.cuda.synchronize()
+    return tuple(np.asarray(r) for r in res)
+
+
+def alg_check(name, k, res):
+    """the result of alg_run against the reference of the operation's own test file, at that file's bar"""
+    h = ES.alg(k)
+    M, dt = h.M, h.dtype
+    cplx = dt.kind == "c"
+    host = lambda r, like=M: O.Bcsr(like.row_sizes, like.col_sizes, *r[-4:])
+
+    def same_matrix(r, want):
+        MO.same_index(host(r, want), want)
+        assert MN.same_bits(r[-1], want.data), "%s of %r: the index is the reference's, the values are not" % (name, h)
+
+    kept_index = lambda r: MO.same_index(host(r), M) is None
+    if name in ("add_flat", "add_union"):
+        ref, scale = MO.reference_add(M, h.T if name == "add_flat" else h.Q, *alg_scalar(h, name))
+        MO.same_index(host(res), ref)
+        assert np.all(np.abs(res[-1] - ref.data) <= 4 * MO.factor(dt) * MO.unit(dt) * scale)
+    elif name == "scale":
+        al = alg_scalar(h, name)
+        assert kept_index(res) and np.all(np.abs(res[-1] - MO.times(al, M.data, dt)) <= 2 * MO.factor(dt) * MO.unit(dt) * abs(al) * np.abs(M.data))
+    elif name == "add_on_diag":
+        al = alg_scalar(h, name)
+        at, _ = MN.diagonal_places(M)
+        off = np.ones(M.data.size, bool)
+        off[at] = False
+        assert kept_index(res) and MN.same_bits(res[-1][off], M.data[off]), "everything off the diagonal stays as it is"
+        ref = (M.data[at] + np.asarray(al, dt)).astype(dt)
+        assert np.all(np.abs(res[-1][at] - ref) <= 4 * MO.factor(dt) * MO.unit(dt) * (np.abs(M.data[at]) + abs(al)))
+    elif name == "trace":
+        at, _ = MN.diagonal_places(M)
+        got = res[0].item()
+        if cplx:
+            MO.check_sum(got.real, M.data[at].real)
+            MO.check_sum(got.imag, M.data[at].imag)
+        else:
+            MO.check_sum(got, M.data[at])
+    elif name == "dot":
+        bx, by = MO.blocks_of(M), MO.blocks_of(h.Q)
+        MO.check_sum(res[0].item(), np.concatenate([bx[key].astype(np.float64) * by[key].astype(np.float64) for key in sorted(set(bx) & set(by))]))
+    elif name == "frobenius_norm":
+        terms = MO.real_terms(M.data)
+        ref = math.sqrt(math.fsum(terms.tolist()))
+        assert abs(res[0].item() - ref) <= (len(terms) + 5) * MO.U53 * ref
+    elif name == "maxabs_norm":
+        ref = float(np.max(np.abs(M.data)))
+        assert abs(res[0].item() - ref) <= 4 * MN.U53 * ref if cplx else res[0].item() == ref
+    elif name == "gershgorin_norm":
+        refs, bars = MN.reference_sums(MN.dense(M), MN.pattern_mask(M), 0, 0)
+        assert abs(res[0].item() - float(np.max(refs))) <= float(np.max(bars))
+    elif name == "norm_column":
+        mask = MN.pattern_mask(M)
+        refs, _ = MN.reference_sums(MN.dense(M), mask, 1, 1)
+        counts = MN.real_terms(np.ones(1, dt)).size * mask.sum(axis=0)
+        MN.check_vector(res[0], np.sqrt(refs), (counts + 5) * MN.U53 * np.sqrt(refs), "column norms")
+    elif name == "get_diag":
+        assert MN.same_bits(res[0], np.ascontiguousarray(np.diagonal(MN.dense(M))).astype(dt))
+    elif name == "set_diag":
+        at, idx = MN.diagonal_places(M)
+        area = M.data.copy()
+        area[at] = alg_vectors(h, name)[0][idx]
+        assert kept_index(res) and MN.same_bits(res[-1], area)
+    elif name == "scale_by_vector":
+        ref, scale = MN.scaled_area(M, alg_vectors(h, name)[0], "right")
+        assert kept_index(res) and (np.all(np.abs(res[-1] - ref) <= 4 * MN.U53 * scale) if cplx else MN.same_bits(res[-1], ref))
+    elif name == "matvec":
+        x, y = alg_vectors(h, name)
+        ref, bar = MV.reference(MV.dense_parts(M, "N"), "T", *alg_scalar(h, name), x, y)
+        MV.within(res[0], ref, bar, "matvec")
+    elif name == "multivec":
+        x, y = alg_vectors(h, name)
+        ref, bar = MVV.reference_columns(MV.dense_parts(M, "N"), "N", *alg_scalar(h, name), x, y)
+        MVV.within_columns(res[0], ref, bar, "multivec")
+    elif name == "rank_update":
+        x, y = alg_vectors(h, name)
+        F, absF, mask = RU.parts_of(M)
+        ref, bar = RU.reference(F, absF, *alg_scalar(h, name), x, y, "T")
+        assert kept_index(res)
+        RU.stored_within(res[-1], M, ref, bar, mask, "rank update")
+    elif name == "get_block_diag":
+        same_matrix(res, MN.subset(M, lambda r, c: r == c))
+    elif name == "invert_block_diag":
+        assert (res[0].item(), res[1].item()) == (0, -1) and kept_index(res)
+        BI.check_inverses(M, host(res), "alg[%d]" % k)
+        assert BI.others_kept(M, host(res))
+    elif name == "scale_by_block_diag":
+        ref, bar = BS.reference(MN.dense(M).astype(BS.wide(dt)), alg_block_diag(h), "left", "T", alg_scalar(h, name), dt)
+        assert kept_index(res)
+        BS.stored_within(res[-1], M, ref, bar, MN.pattern_mask(M), "block scale")
+    elif name == "to_dense":
+        assert MN.same_bits(res[0], MN.dense(M))
+    elif name == "from_dense":
+        assert kept_index(res) and MN.same_bits(res[-1], GD.expected_area(M, M.data, alg_vectors(h, name)[0]))
+    elif name == "create_from_dense":
+        same_matrix(res, GD.filtered_host(MN.dense(h.Q), h.sizes, h.sizes, GD.EPS))
+    elif name in ("hadamard_flat", "hadamard_two_patterns"):
+        EW.assert_product(host(res), M, h.T if name == "hadamard_flat" else h.Q, None)
+    elif name == "copy_keep_sparsity":
+        assert kept_index(res) and R.same_bits(res[-1], R.reference_copy_onto(h.Q, M))
+    elif name == "function_of_elements":
+        assert EW.function_excess(h.F, *ES.ALG_FUNCTION, res[-1]) <= (1 if dt == np.float32 else EW.C64)
+    elif name == "submatrix_gather":
+        assert MN.same_bits(res[0], SR.gathered(M, "N", h.sets, h.subs, h.sub_n, 1.0))
+    elif name == "submatrix_scatter":
+        area, written = SR.scattered_area(M, M.data, h.sets, h.owner, alg_vectors(h, name)[0], h.subs)
+        assert written and kept_index(res) and MN.same_bits(res[-1], area)
+    elif name == "submatrix_apply":
+        D = MN.dense(M)
+        windows = [np.ascontiguousarray(SR.window(D, S, h.sizes, int(SR.elements_of(S, h.sizes).size), 1.0).T) for S in h.group_sets]
+        area, written = SR.scattered_area(M, M.data, h.group_sets, h.group_owner, windows)
+        assert written and kept_index(res) and MN.same_bits(res[-1], area)
+    elif name == "filtered":
+        keep = ~(ES.block_sq_moduli(M) < h.eps * h.eps)
+        assert 0 < keep.sum() < keep.size
+        same_matrix(res, ES.subset(M, keep))
+    elif name == "cropped":
+        same_matrix(res, O.crop(M, *h.crop))
+    elif name == "transposed":
+        same_matrix(res, O.transposed(M))
+    elif name == "desymmetrized":
+        got = host(res)
+        assert got.nblks == 2 * h.tri.nblks - h.nb and np.array_equal(got.blk_p, np.concatenate([[0], np.cumsum(FIP.block_sizes(got))[:-1]]))
+        assert MN.same_bits(MN.dense(got), MN.desymmetrized_dense(h.tri, h.symmetry).astype(dt))
+    else:
+        raise AssertionError(name)
+
+
+@pytest.fixture(scope="module")
+def fresh_alg():
+    """fresh_alg(name, k): the operation on pool matrix k on an engine of its own, computed once and checked once against its reference"""
+    cache = {}
+
+    def get(name, k):
+        if (name, k) not in cache:
+            cache[name, k] = alg_run(name, MultiplyEngine(), k)
+            alg_check(name, k, cache[name, k])
+        return cache[name, k]
+
+    return get
+
+
+@pytest.mark.parametrize("name", list(ES.ALG_WALKS))
+def test_algebra_walk_on_one_engine(name, fresh, fresh_alg):
+    eng = MultiplyEngine()
+    same_result(9, run(eng, 9), fresh(9), "before the %s walk of the algebra" % name)
+    for step, (op, k) in enumerate(ES.ALG_WALKS[name]):
+        got, want = alg_run(op, eng, k), fresh_alg(op, k)
+        assert len(got) == len(want) and all(same_bits(g, w) for g, w in zip(got, want)), \
+            "%s step %d: %s of %r gives other bits than on a fresh engine" % (name, step, op, ES.alg(k))
+    same_result(9, run(eng, 9), fresh(9), "after the %s walk of the algebra" % name)
