@@ -15,6 +15,8 @@ from .operations import dbcsr_create_from_dense, dbcsr_from_dense, dbcsr_to_dens
 from .operations import dbcsr_copy, dbcsr_function_of_elements, dbcsr_hadamard_product  # noqa: F401
 from .operations import (dbcsr_func_artanh, dbcsr_func_asin, dbcsr_func_cos, dbcsr_func_dcos, dbcsr_func_ddcos, dbcsr_func_ddsin,  # noqa: F401
                          dbcsr_func_ddtanh, dbcsr_func_dsin, dbcsr_func_dtanh, dbcsr_func_inverse, dbcsr_func_sin, dbcsr_func_tanh)
+from .operations import (dbcsr_create_from_blocks, dbcsr_get_blocks, dbcsr_put_blocks, dbcsr_reserve_all_blocks,  # noqa: F401
+                         dbcsr_reserve_blocks, dbcsr_reserve_diag_blocks)
 from .submatrix import SubmatrixPlan, dbcsr_submatrix_apply, dbcsr_submatrix_gather, dbcsr_submatrix_plan, dbcsr_submatrix_scatter  # noqa: F401
 
 __all__ = ["load_library", "library_path", "dbcsr_add", "dbcsr_scale", "dbcsr_add_on_diag", "dbcsr_trace", "dbcsr_dot", "dbcsr_frobenius_norm",
@@ -24,4 +26,6 @@ __all__ = ["load_library", "library_path", "dbcsr_add", "dbcsr_scale", "dbcsr_ad
            "dbcsr_hadamard_product", "dbcsr_copy", "dbcsr_function_of_elements", "dbcsr_func_inverse", "dbcsr_func_tanh", "dbcsr_func_dtanh",
            "dbcsr_func_ddtanh", "dbcsr_func_artanh", "dbcsr_func_sin", "dbcsr_func_dsin", "dbcsr_func_ddsin", "dbcsr_func_asin", "dbcsr_func_cos",
            "dbcsr_func_dcos", "dbcsr_func_ddcos",
+           "dbcsr_reserve_blocks", "dbcsr_put_blocks", "dbcsr_get_blocks", "dbcsr_reserve_diag_blocks", "dbcsr_reserve_all_blocks",
+           "dbcsr_create_from_blocks",
            "SubmatrixPlan", "dbcsr_submatrix_plan", "dbcsr_submatrix_gather", "dbcsr_submatrix_scatter", "dbcsr_submatrix_apply"]

@@ -67,6 +67,7 @@
 #include "mm_aux.h"
 #include "mm_algebra.h"   // add, add_on_diag, trace, dot, norm: the operations between multiplies (brings mm_block_walk.h: Pack16, walk_block)
 #include "mm_elementwise.h"  // element-wise operations on two patterns: hadamard product, copy onto a pattern, functions of elements
+#include "mm_blocklist.h"  // a coordinate list of blocks: reserve, put and get
 #include "mm_multivec.h"  // the matrix times several dense vectors
 #include "mm_rank_update.h"  // the rank-k update on the stored pattern
 #include "mm_block_inverse.h"  // the block diagonal: its copy and the batched inverse of its blocks
@@ -619,6 +620,7 @@ int dbcsr_amd_mm_numeric_z(void* handle, const double alpha[2], const dbcsr_amd_
 #include "mm_engine_ops.h"   // init_c, crop, filter, checksum, fill, transpose, twin moves, statistics
 #include "mm_engine_algebra.h"   // add, add_on_diag, trace, dot, norm
 #include "mm_engine_elementwise.h"   // hadamard product, copy onto a pattern, functions of elements
+#include "mm_engine_blocklist.h"   // reserve, put and get blocks through a coordinate list
 
 }  // extern "C"
 

@@ -151,6 +151,5 @@ int dbcsr_amd_bcsr_function_of_elements(void* handle, libsmm_acc_data_t datatype
   else function_launch<float>(st, m, func, a0, a1);
   return check(hipGetLastError(), "dbcsr_amd_bcsr_function_of_elements", __FILE__, __LINE__);
 }
-#undef DBCSR_AMD_BY_TYPE
 
 #endif

@@ -166,6 +166,18 @@ struct Engine {
   int had_assumed = 0;
   int64_t had_nblks_a = 0, had_nblks_b = 0, had_nblks = 0, had_nze = 0;
 
+  // ---- block lists (mm_engine_blocklist.h): reserve, put and get through a coordinate list of blocks, in buffers and fields that no other entry writes --
+  // a put between the two halves of an add, a hadamard product, a filter or a twin move changes nothing of theirs, and these change nothing here.  A
+  // reserve count that found blocks to create has gone on into the symbolic phase's work areas (cin_bm, c_bm, cin_pre, c_pre, c_blk_p_ws), as the union
+  // add does: engine_takes_work_areas ends it ----
+  DevBuf<uint32_t> bl_bm;     // reserve: the bits of the listed blocks the matrix lacks [nblkrows][W]
+  DevBuf<unsigned long long> bl_cnt;   // reserve: blocks to create, invalid entries, elements of the new blocks, elements the matrix names
+  DevBuf<int> bl_i32;         // put: hit[n], slots[n], order[n], cnt[nblks + 1], seg[nblks + 1]
+  bool rsv_pending = false;   // a dbcsr_amd_bcsr_reserve_count found blocks to create and nothing has taken the work areas since
+  const void* rsv_row_p = nullptr;   // ... for the matrix with this row_p, these sizes and this many blocks
+  int rsv_nblkrows = 0, rsv_nblkcols = 0;
+  int64_t rsv_nblks_a = 0, rsv_nblks = 0, rsv_nze = 0;
+
   // ---- switches (mm_engine_env.h) ----
   Switches sw;      // the numeric phase's kernel families (mm_choose.h)
   LabSwitches lab;  // lab build only: no state in the shipping build
@@ -203,7 +215,7 @@ static inline void engine_writes_values(Engine* E) { E->norms_data = nullptr; }
 // The count halves of the two-call protocols (filter, crop, union add, twin / desymmetrize) leave their answer in work areas that the symbolic phase, each
 // other's count and the transpose write too.  Whoever is about to write those areas calls this first: a count that is still pending is over, and its
 // apply half then refuses (-1) and writes nothing instead of compacting by what this call left there.  Every apply half asks for a pending count of ITS
-// OWN pair (flt_pending, crop_pending, add_mode, twin_mode), never for a block count alone: a crop count of a matrix with as many blocks as the filter's
+// OWN pair (flt_pending, crop_pending, add_mode, twin_mode, rsv_pending), never for a block count alone: a crop count of a matrix with as many blocks as the filter's
 // ends the filter's count like any other.  The filter's and the twin's counts stay pending after an apply (the apply may be repeated); a count of a twin
 // is pending for one matrix shape (nblks, nblkrows) and one mode.
 static inline void engine_takes_work_areas(Engine* E) {
@@ -213,6 +225,7 @@ static inline void engine_takes_work_areas(Engine* E) {
   E->crop_pending = false;
   E->twin_mode = -1;
   if (E->add_mode == 2) E->add_mode = 0;
+  E->rsv_pending = false;
 }
 
 KPassMemo* engine_kpass_memo(void* handle) { return handle ? &static_cast<Engine*>(handle)->kpass_memo : nullptr; }

@@ -56,6 +56,8 @@ MM_SYMBOLS = [
     "dbcsr_amd_bcsr_submatrix_gather", "dbcsr_amd_bcsr_submatrix_scatter",
     # element-wise operations on two patterns
     "dbcsr_amd_bcsr_hadamard_count", "dbcsr_amd_bcsr_hadamard_apply", "dbcsr_amd_bcsr_copy_onto", "dbcsr_amd_bcsr_function_of_elements",
+    # block lists: reserve, put and get through a coordinate list of blocks
+    "dbcsr_amd_bcsr_reserve_count", "dbcsr_amd_bcsr_reserve_apply", "dbcsr_amd_bcsr_put_blocks", "dbcsr_amd_bcsr_get_blocks",
 ]
 
 # `kind` of a matrix with symmetry in the C ABI (include/dbcsr_amd_mm.h): bit 0 negates the twin block, bit 1 conjugates it
@@ -234,6 +236,10 @@ def load_library(lab=False):
     L.dbcsr_amd_bcsr_hadamard_apply.argtypes = [vp, i32, BP, BP, Z, BP, vp]
     L.dbcsr_amd_bcsr_copy_onto.argtypes = [vp, i32, BP, BP, vp]
     L.dbcsr_amd_bcsr_function_of_elements.argtypes = [vp, i32, BP, i32, C.c_double, C.c_double, vp]
+    L.dbcsr_amd_bcsr_reserve_count.argtypes = [vp, BP, i64, vp, vp, i32, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), vp]
+    L.dbcsr_amd_bcsr_reserve_apply.argtypes = [vp, i32, BP, BP, vp]
+    L.dbcsr_amd_bcsr_put_blocks.argtypes = [vp, i32, BP, i64, vp, vp, vp, vp, Z, i32, vp]
+    L.dbcsr_amd_bcsr_get_blocks.argtypes = [vp, i32, BP, i64, vp, vp, vp, vp, vp, vp]
     if lab:   # diagnostics of the experimental dataflows (dbcsr_amd/csrc/mm_lab_api.h): the shipping build does not export them
         L.dbcsr_amd_mm_tile_stats.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
         L.dbcsr_amd_mm_band_stats.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]

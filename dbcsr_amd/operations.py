@@ -24,6 +24,11 @@
     dbcsr_hadamard_product(matrix_a, matrix_b, matrix_c, b_assume_value)  C <- A o B on the blocks both store (or on A's, B's missing blocks assumed)
     dbcsr_copy(matrix_b, matrix_a, keep_sparsity)               B <- A; keep_sparsity: A projected onto B's pattern, in place
     dbcsr_function_of_elements(matrix_a, func, a0, a1)          x <- f(a1*x + a0) in place, func one of dbcsr_func_*                 (real data)
+    dbcsr_reserve_blocks(matrix, rows, cols)                    the pattern grows by a list of blocks, new blocks are zero; returns the number created
+    dbcsr_put_blocks(matrix, rows, cols, data, offsets, summation, alpha, keep_sparsity)  A_rc <- [A_rc +] alpha*X per list entry, in list order (dbcsr_put_block)
+    dbcsr_get_blocks(matrix, rows, cols, out, offsets)          (data, found): the listed blocks bit for bit, zero where absent (dbcsr_get_block_p)
+    dbcsr_reserve_diag_blocks(matrix) / dbcsr_reserve_all_blocks(matrix)  the diagonal / every block reserved
+    dbcsr_create_from_blocks(row_blk_size, col_blk_size, rows, cols, data, offsets, summation)  a new matrix from a list of blocks
 
 Same argument names and error behaviour; the work is done by the C-ABI engine (include/dbcsr_amd_mm.h, "Matrix algebra between
 multiplies") on the GPU, for float64, float32 and complex128 data.  One rank / one device here: of a distributed matrix trace, dot
@@ -1001,3 +1006,233 @@ def dbcsr_function_of_elements(matrix_a, func, a0=0.0, a1=1.0, a2=None, engine=N
     rc = E.L.dbcsr_amd_bcsr_function_of_elements(E.h, code, C.byref(d), int(func), float(a0), float(a1), st.ptr)
     if rc != 0:
         raise RuntimeError("dbcsr_amd_bcsr_function_of_elements failed (%d)" % rc)
+
+
+# ---- block lists: reserve, put and get through a coordinate list of blocks ----------------------------------------------------------------------------------
+def _on_stream(stream):
+    return torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream())
+
+
+def _check_list(name, matrix, rows, cols):
+    """rows / cols of a block list: 1-D int32 tensors of one length on the matrix' device (TypeError for what is no int32 tensor, ValueError otherwise);
+    returns them contiguous and their length"""
+    for what, t in (("rows", rows), ("cols", cols)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+            raise TypeError("%s: %s must be an int32 torch tensor" % (name, what))
+        if t.dim() != 1:
+            raise ValueError("%s: %s must be 1-D, got %d dimensions" % (name, what, t.dim()))
+    if rows.numel() != cols.numel():
+        raise ValueError("%s: rows and cols differ in length (%d, %d)" % (name, rows.numel(), cols.numel()))
+    for what, t in (("rows", rows), ("cols", cols)):
+        if t.device != matrix.row_p.device:
+            raise ValueError("%s: %s is not on the matrix' device" % (name, what))
+    if rows.numel() > 2 ** 31 - 1:
+        raise ValueError("%s: a list of %d entries" % (name, rows.numel()))
+    return rows.contiguous(), cols.contiguous(), int(rows.numel())
+
+
+def _check_offsets(name, offsets, n, device):
+    if not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int64:
+        raise TypeError("%s: offsets must be an int64 torch tensor" % name)
+    if offsets.dim() != 1 or offsets.numel() != n:
+        raise ValueError("%s: offsets must be 1-D with one entry per block of the list" % name)
+    if offsets.device != device:
+        raise ValueError("%s: offsets is not on the matrix' device" % name)
+    return offsets.contiguous()
+
+
+def _check_flat(name, what, t, matrix):
+    if not isinstance(t, torch.Tensor) or t.dtype != matrix.dtype:
+        raise TypeError("%s: %s must be a torch tensor of the matrix' data type" % (name, what))
+    if t.dim() != 1 or not t.is_contiguous():
+        raise ValueError("%s: %s must be a flat (1-D, contiguous) tensor" % (name, what))
+    if t.device != matrix.row_p.device:
+        raise ValueError("%s: %s is not on the matrix' device" % (name, what))
+
+
+def _list_windows(matrix, rows, cols, offsets, extent):
+    """(rows as the kernels are to see them, offsets, end of the last window or None) of a list, formed with torch on the device without a
+    synchronisation.  The size of entry i's window is row_blk_size[rows[i]] * col_blk_size[cols[i]], zero for a coordinate outside the matrix; offsets
+    None: the windows one after another.  With an extent (the length of the flat tensor) an entry whose window does not lie inside [0, extent) is
+    given the row -1, which every kernel skips: nothing is ever read or written outside the tensor."""
+    nbr, nbc = matrix.nblkrows, matrix.nblkcols
+    if nbr == 0 or nbc == 0:
+        sizes = torch.zeros(rows.numel(), dtype=torch.int64, device=rows.device)
+    else:
+        ok = (rows >= 0) & (rows < nbr) & (cols >= 0) & (cols < nbc)
+        r, c = rows.clamp(0, nbr - 1).long(), cols.clamp(0, nbc - 1).long()
+        sizes = torch.where(ok, matrix.row_blk_size[r].long() * matrix.col_blk_size[c].long(), torch.zeros((), dtype=torch.int64, device=rows.device))
+    if offsets is None:
+        ends = torch.cumsum(sizes, 0)
+        offsets = ends - sizes
+    else:
+        ends = offsets + sizes
+    if extent is not None:
+        inside = (offsets >= 0) & (ends <= extent)
+        rows = torch.where(inside, rows, torch.full((), -1, dtype=torch.int32, device=rows.device))
+    return rows, offsets, ends
+
+
+def dbcsr_reserve_blocks(matrix, rows, cols, engine=None, stream=None):
+    """The pattern grows (dbcsr_reserve_blocks): afterwards the matrix stores every block it stored and every block (rows[i], cols[i]) of the list --
+    int32 device tensors, any order, duplicates allowed.  Every stored block keeps its bits, every new block is +0.0; the result is packed with
+    ascending block columns per row and handed to the matrix with adopt, as the add does.  Returns the number of blocks created.  When the list names
+    no block the matrix lacks -- the usual case inside an iteration -- nothing is written: the same tensor objects stay, index_stamp() is unchanged and
+    a multiply that had the matrix as operand still reuses its plan.  A coordinate outside [0, nblkrows) x [0, nblkcols), or below the diagonal of a
+    matrix with symmetry ('S' 'A' 'H' 'K': the stored triangle is served as it is, a block is not transposed onto its twin), raises ValueError and
+    leaves the matrix unchanged.  float64, float32 and complex128.  Synchronises once."""
+    fn = "dbcsr_reserve_blocks"
+    rows, cols, n = _check_list(fn, matrix, rows, cols)
+    sym = _check_symmetry(fn, matrix)
+    code = matrix.dtype_code
+    if sym != "N" and matrix.nblkrows != matrix.nblkcols:
+        raise ValueError("%s: a matrix with symmetry %r that is not square" % (fn, sym))
+    if n == 0:
+        return 0
+    E = engine or default_engine()
+    st = StreamHandle(stream)
+    A = matrix
+    dev = A.row_p.device
+    a = A.desc()
+    with _on_stream(stream):
+        row_p = torch.empty(A.nblkrows + 1, dtype=torch.int32, device=dev)
+    nb, nz, new, bad = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+    rc = E.L.dbcsr_amd_bcsr_reserve_count(E.h, C.byref(a), n, rows.data_ptr(), cols.data_ptr(), 0 if sym == "N" else 1, row_p.data_ptr(), C.byref(nb),
+                                          C.byref(nz), C.byref(new), C.byref(bad), st.ptr)
+    if rc != 0:
+        raise RuntimeError("dbcsr_amd_bcsr_reserve_count failed (%d)" % rc)
+    if bad.value:
+        raise ValueError("%s: %d of %d coordinates lie outside the %d x %d blocks of the matrix%s" %
+                         (fn, bad.value, n, A.nblkrows, A.nblkcols, "" if sym == "N" else " or below the diagonal of its stored triangle"))
+    if new.value == 0:
+        return 0
+    with _on_stream(stream):
+        out = DbcsrMatrix(A.row_blk_size, A.col_blk_size, row_p, torch.empty(nb.value, dtype=torch.int32, device=dev),
+                          torch.empty(nb.value, dtype=torch.int64, device=dev), torch.empty(nz.value, dtype=A.dtype, device=dev), A.name)
+    dst = out.desc(out=True)
+    rc = E.L.dbcsr_amd_bcsr_reserve_apply(E.h, code, C.byref(a), C.byref(dst), st.ptr)
+    if rc != 0:
+        raise RuntimeError("dbcsr_amd_bcsr_reserve_apply failed (%d)" % rc)
+    matrix.adopt(out)   # as a multiply hands its result to matrix_c
+    return int(new.value)
+
+
+def dbcsr_put_blocks(matrix, rows, cols, data, offsets=None, summation=False, alpha=1.0, keep_sparsity=False, engine=None, stream=None):
+    """Blocks into the matrix (dbcsr_put_block with summation and scale, for a whole list at once): per entry A_rc <- A_rc + alpha*X with summation,
+    A_rc <- alpha*X without.  rows, cols: int32 device tensors, any order, duplicates allowed; data: one flat tensor of the matrix' type that holds
+    the blocks, each column-major as the library stores blocks; offsets: int64 device tensor of the element offsets of the blocks in data, None: one
+    block after another in list order.  keep_sparsity=False first reserves the listed blocks (dbcsr_reserve_blocks: its errors, its one
+    synchronisation, and a new index only when the pattern grows); with True, entries whose block the matrix does not store are skipped.
+    Contributions to one block are applied in list order: with summation all are added in that order, without it the last of the list wins.  The
+    same bits on every call.  With alpha == 1 nothing is multiplied: an overwrite is bit for bit, a sum is the type's own addition.  The put itself
+    never synchronises and writes no index array: index_stamp() stays, holes of an unpacked matrix keep their bits, and a multiply afterwards reuses
+    its plan when the pattern held.  An entry whose window does not lie inside data is skipped (checked on the device, nothing outside data is read).
+    data sharing memory with the matrix' data area: ValueError.  float64, float32 and complex128."""
+    fn = "dbcsr_put_blocks"
+    rows, cols, n = _check_list(fn, matrix, rows, cols)
+    _check_flat(fn, "data", data, matrix)
+    if offsets is not None:
+        offsets = _check_offsets(fn, offsets, n, matrix.row_p.device)
+    _check_symmetry(fn, matrix)
+    _check_scalar(fn, matrix, alpha)
+    code = matrix.dtype_code
+    if _data_overlap(data, matrix.data):
+        raise ValueError("%s: data shares memory with the matrix' data area" % fn)
+    if n == 0:
+        return
+    if not keep_sparsity:
+        dbcsr_reserve_blocks(matrix, rows, cols, engine=engine, stream=stream)
+    E = engine or default_engine()
+    st = StreamHandle(stream)
+    with _on_stream(stream):
+        seen, offsets, _ = _list_windows(matrix, rows, cols, offsets, int(data.numel()))
+    d = matrix.desc()   # (only the data area is written)
+    rc = E.L.dbcsr_amd_bcsr_put_blocks(E.h, code, C.byref(d), n, seen.data_ptr(), cols.data_ptr(), offsets.data_ptr(),
+                                       data.data_ptr() if data.numel() else None, _z(alpha), 1 if summation else 0, st.ptr)
+    if rc != 0:
+        raise RuntimeError("dbcsr_amd_bcsr_put_blocks failed (%d)" % rc)
+
+
+def dbcsr_get_blocks(matrix, rows, cols, out=None, offsets=None, engine=None, stream=None):
+    """Blocks out of the matrix (dbcsr_get_block_p, for a whole list at once): returns (data, found).  Every listed block is copied bit for bit into the
+    flat tensor data at its offset (offsets as in dbcsr_put_blocks; None: one block after another) and found[i] (int32, device) is 1; where the
+    matrix stores no such block the window is +0.0 and found[i] is 0; a coordinate outside the matrix has no window and found[i] is 0.  Every element
+    of every window is written exactly once, nothing outside; duplicates are fine, each has its window.  out: the flat tensor to write into (then
+    nothing synchronises; an entry whose window does not lie inside out is treated as out of range; windows that overlap each other are the caller's
+    error; out sharing memory with the matrix' data area: ValueError); None: a tensor of the needed length is made, zero between windows, which costs
+    one synchronisation for its length.  Uses no saved plan and no work area.  float64, float32 and complex128."""
+    fn = "dbcsr_get_blocks"
+    rows, cols, n = _check_list(fn, matrix, rows, cols)
+    if out is not None:
+        _check_flat(fn, "out", out, matrix)
+    if offsets is not None:
+        offsets = _check_offsets(fn, offsets, n, matrix.row_p.device)
+    _check_symmetry(fn, matrix)
+    code = matrix.dtype_code
+    if out is not None and _data_overlap(out, matrix.data):
+        raise ValueError("%s: out shares memory with the matrix' data area" % fn)
+    dev = matrix.row_p.device
+    E = engine or default_engine()
+    st = StreamHandle(stream)
+    with _on_stream(stream):
+        found = torch.empty(n, dtype=torch.int32, device=dev)
+        if n == 0:
+            return (out if out is not None else torch.empty(0, dtype=matrix.dtype, device=dev)), found
+        if out is None:
+            given = offsets is not None
+            _, offsets, ends = _list_windows(matrix, rows, cols, offsets, None)
+            if given and int(offsets.min()) < 0:
+                raise ValueError("%s: a negative offset" % fn)
+            length = max(int(ends.max()), 0)
+            out = torch.zeros(length, dtype=matrix.dtype, device=dev) if given else torch.empty(length, dtype=matrix.dtype, device=dev)
+            seen = rows
+        else:
+            seen, offsets, _ = _list_windows(matrix, rows, cols, offsets, int(out.numel()))
+    d = matrix.desc()
+    rc = E.L.dbcsr_amd_bcsr_get_blocks(E.h, code, C.byref(d), n, seen.data_ptr(), cols.data_ptr(), offsets.data_ptr(),
+                                       out.data_ptr() if out.numel() else None, found.data_ptr(), st.ptr)
+    if rc != 0:
+        raise RuntimeError("dbcsr_amd_bcsr_get_blocks failed (%d)" % rc)
+    return out, found
+
+
+def dbcsr_reserve_diag_blocks(matrix, engine=None, stream=None):
+    """dbcsr_reserve_diag_blocks: every diagonal block (i, i), i below min(nblkrows, nblkcols), is stored afterwards; returns the number created."""
+    k = min(matrix.nblkrows, matrix.nblkcols)
+    with _on_stream(stream):
+        d = torch.arange(k, dtype=torch.int32, device=matrix.row_p.device)
+    return dbcsr_reserve_blocks(matrix, d, d, engine=engine, stream=stream)
+
+
+def dbcsr_reserve_all_blocks(matrix, engine=None, stream=None):
+    """dbcsr_reserve_all_blocks: every block is stored afterwards -- of a matrix with symmetry every block of the stored (upper) triangle; returns the
+    number created."""
+    nbr, nbc = matrix.nblkrows, matrix.nblkcols
+    if nbr * nbc > 2 ** 31 - 1:
+        raise ValueError("dbcsr_reserve_all_blocks: a block structure of %d x %d blocks" % (nbr, nbc))
+    with _on_stream(stream):
+        t = torch.arange(nbr * nbc, dtype=torch.int64, device=matrix.row_p.device)
+        r, c = (t // max(nbc, 1)).to(torch.int32), (t % max(nbc, 1)).to(torch.int32)
+        if _check_symmetry("dbcsr_reserve_all_blocks", matrix) != "N":
+            upper = c >= r
+            r, c = r[upper], c[upper]
+    return dbcsr_reserve_blocks(matrix, r, c, engine=engine, stream=stream)
+
+
+def dbcsr_create_from_blocks(row_blk_size, col_blk_size, rows, cols, data, offsets=None, summation=True, name="", engine=None, stream=None):
+    """A new packed matrix without symmetry from a list of blocks: an empty matrix of these block sizes, then dbcsr_put_blocks(rows, cols, data,
+    offsets, summation) onto it -- the device-side from_host for callers who hold blocks, not CSR arrays.  Blocks named more than once are summed in
+    list order (summation=True) or the last one wins.  The block sizes: int32 device tensors as the matrices hold them (taken as they are), or any
+    sequence of integers.  data: a flat device tensor (float64, float32 or complex128)."""
+    fn = "dbcsr_create_from_blocks"
+    if not isinstance(data, torch.Tensor):
+        raise TypeError("%s: data must be a torch tensor" % fn)
+    _dtype_code(data.dtype)
+    if data.device.type != "cuda":
+        raise ValueError("%s: data is not on a GPU" % fn)
+    dev = data.device
+    rs, cs = _block_sizes(fn, "row_blk_size", row_blk_size, dev), _block_sizes(fn, "col_blk_size", col_blk_size, dev)
+    with _on_stream(stream):
+        M = DbcsrMatrix.empty_like_pattern(rs, cs, data.dtype, device=dev, name=name)
+    dbcsr_put_blocks(M, rows, cols, data, offsets=offsets, summation=summation, engine=engine, stream=stream)
+    return M

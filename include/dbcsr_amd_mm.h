@@ -595,6 +595,44 @@ enum {
 };
 int dbcsr_amd_bcsr_function_of_elements(void* handle, libsmm_acc_data_t datatype, dbcsr_amd_bcsr* m, int func, double a0, double a1, void* stream);
 
+/* Block lists (src/block/dbcsr_block_access.F: dbcsr_reserve_blocks, dbcsr_put_block with summation and scale, dbcsr_get_block_p; the merge of the work
+ * matrices in dbcsr_finalize), for the types of the algebra above (any other type code: -10).  A list is rows[n], cols[n] (int32, device): entry i names
+ * block (rows[i], cols[i]); any order, duplicates allowed.  Put and get move the blocks through ONE flat area of the matrix' type: entry i's window starts
+ * at element off[i] (int64, device) of it and holds rs[rows[i]] * cs[cols[i]] elements, column-major as the library stores blocks.  Every operation goes by
+ * the index and relies on ascending block columns per block row.  A matrix with symmetry is served on its stored triangle as it is: a block below the
+ * diagonal is not transposed onto its twin.  NULL arguments, n < 0, more than 2^31 - 1 entries or blocks: -1.
+ *
+ * dbcsr_reserve_blocks: the pattern grows to the union of the matrix' pattern and the list.  Every block the matrix stores keeps its bits, every new block
+ * is +0.0, the result is packed with ascending block columns per row.  Two steps, as add / filter / crop:
+ *   _reserve_count  counts (host; synchronises once): *n_invalid entries outside [0, nblkrows) x [0, nblkcols), or with upper_only != 0 (square matrices
+ *     only: the stored triangle of a matrix with symmetry) below the diagonal -- with any of them nothing is pending and the caller refuses the list;
+ *     *n_new blocks the list names and the matrix lacks (a block named twice counts once).  *n_new == 0: there is nothing to apply, and no work area
+ *     of the symbolic phase and no saved plan was touched -- a multiply afterwards reuses its plan.  Otherwise *nblks / *nze are the counts of the
+ *     result, dst_row_p [nblkrows + 1] (device) receives its row_p, and the call has taken the symbolic phase's work areas and invalidated the saved
+ *     plan, as the union add does.
+ *   _reserve_apply  fills dst (dst->row_p = that row_p; col_i, blk_p [nblks], data [nze] allocated by the caller; dst's data area is not m's).
+ *     Asynchronous on stream.  One _apply per _count: an _apply without a pending _count, after anything else took the work areas, or for a matrix
+ *     other than the counted one (row_p, sizes, block count) is refused (-1) and writes nothing.  What is pending lives in fields of its own; a put, a get
+ *     or a norm between the two halves disturbs nothing.
+ *
+ * dbcsr_put_block: per entry A_rc <- A_rc + alpha X (summation != 0) or A_rc <- alpha X.  Entries out of range or whose block the matrix does not store
+ * are skipped.  Contributions to one block are applied IN LIST ORDER: with summation all of them are added in that order, without it the last one of the
+ * list wins.  With alpha exactly 1 nothing is multiplied: an overwrite is bit for bit, a sum is the type's own addition.  The same bits on every call; no
+ * floating-point atomics.  Only elements the index names are written (holes keep their bits), no index array is written, nothing synchronises, no work
+ * area of the symbolic phase and no saved plan is touched: asynchronous on stream.  The windows must lie inside src and src must not overlap the matrix'
+ * data area (the caller's contract).
+ *
+ * dbcsr_get_block_p: every window <- the block bit for bit and found[i] = 1, or +0.0 and found[i] = 0 where the matrix stores no such block; an entry out
+ * of range has no window (found[i] = 0, nothing else written).  Every element of every window is written exactly once, nothing outside.  The windows
+ * must lie inside dst and must not overlap each other or the matrix' data area (the caller's contract).  No saved plan, no work area: asynchronous. */
+int dbcsr_amd_bcsr_reserve_count(void* handle, const dbcsr_amd_bcsr* m, int64_t n, const int32_t* rows, const int32_t* cols, int upper_only,
+  int32_t* dst_row_p, int64_t* nblks, int64_t* nze, int64_t* n_new, int64_t* n_invalid, void* stream);
+int dbcsr_amd_bcsr_reserve_apply(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, dbcsr_amd_bcsr* dst, void* stream);
+int dbcsr_amd_bcsr_put_blocks(void* handle, libsmm_acc_data_t datatype, dbcsr_amd_bcsr* m, int64_t n, const int32_t* rows, const int32_t* cols,
+  const int64_t* src_off, const void* src, const double alpha[2], int summation, void* stream);
+int dbcsr_amd_bcsr_get_blocks(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, int64_t n, const int32_t* rows, const int32_t* cols,
+  const int64_t* dst_off, void* dst, int32_t* found, void* stream);
+
 /* Measurement helper (bench.py, roofline.fabric): what the L2 <-> Infinity-Cache fabric of the current device delivers, in TB/s -- a
  * plain streaming read of a 160 MB window by all CUs, and the block gather of the block-product dataflow (4232-byte blocks from
  * pseudo-random places of the window into LDS, whole 128-byte lines counted).  Takes well under a second; synchronises the device. */

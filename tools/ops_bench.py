@@ -98,6 +98,18 @@ place) against torch.tanh_ on the data area.  No condition: times, ratios and th
 
     python tools/ops_bench.py --elementwise --alternations 7 --warmup 2 --out profiles/elementwise.txt
 
+With --blocks only the block lists are timed (dbcsr_reserve_blocks, dbcsr_put_blocks, dbcsr_get_blocks; kernels of dbcsr_amd/csrc/mm_blocklist.h),
+alternating with their yardsticks, on the full pattern unless said otherwise and through the C entries: put.over (every block overwritten from a list in
+random order, the source packed in list order: locate, group, apply) and get (every block into windows in list order) against copy_onto
+(dbcsr_copy(keep_sparsity=True) between two matrices of that pattern) and torch.copy_ of the data area; put.sum (summation) against the flat dbcsr_add;
+put.python: the whole dbcsr_put_blocks(keep_sparsity=True) call with the window checks torch does in front of it; reserve.general (count + apply of a
+list that is the general pair's B pattern onto the general pair's A: half of it new) and reserve.count against add.general and add.count of that pair;
+reserve.none (a count over the whole pattern in random order that finds nothing to create) against add.count of two matrices of the same pattern;
+create (dbcsr_create_from_blocks from that list and source, one call per sample, by the host's clock) against from_host of the same matrix from
+pageable numpy arrays, its host-to-device copy included.  No condition: times, ratios and their spread are the result:
+
+    python tools/ops_bench.py --blocks --alternations 7 --warmup 2 --out profiles/block_lists.txt
+
 A sample is `--reps` calls back to back between two device events, divided by reps.  Bytes are counted from the shapes: 8 * (elements read + elements
 written) of the data areas, index arrays left out.  Spread = (max - min) / median over the samples."""
 import argparse
@@ -116,6 +128,7 @@ from dbcsr_amd.multiply import MultiplyEngine, dbcsr_multiply  # noqa: E402
 from dbcsr_amd.operations import dbcsr_add, dbcsr_get_block_diag, dbcsr_invert_block_diag, dbcsr_scale, dbcsr_scale_by_block_diag  # noqa: E402
 from dbcsr_amd.operations import dbcsr_create_from_dense, dbcsr_from_dense, dbcsr_to_dense  # noqa: E402
 from dbcsr_amd.operations import dbcsr_func_tanh, dbcsr_hadamard_product  # noqa: E402
+from dbcsr_amd.operations import dbcsr_create_from_blocks, dbcsr_put_blocks  # noqa: E402
 from dbcsr_amd.submatrix import dbcsr_submatrix_gather, dbcsr_submatrix_plan, dbcsr_submatrix_scatter  # noqa: E402
 
 
@@ -772,6 +785,164 @@ def elementwise(args, say, lines, rng, b, nb, st):
             f.write("\n".join(lines) + "\n")
 
 
+def blocks(args, say, lines, rng, b, nb, st):
+    E = MultiplyEngine()
+    f64 = L.dbcsr_type_real_8
+    mask = rng.random((nb, nb)) < args.fill_flat
+    A, B = matrix_of(mask, b, 1), matrix_of(mask, b, 2)
+    a, b_ = A.desc(), B.desc()
+    u = rng.random((nb, nb))
+    q = args.fill_general / 2
+    mask_b = (u < q) | ((u >= 2 * q) & (u < 3 * q))
+    GA, GB = matrix_of((u < 2 * q), b, 3), matrix_of(mask_b, b, 4)
+    ga, gb = GA.desc(), GB.desc()
+    check = lambda rc: rc == 0 or sys.exit("a library call failed (%d)" % rc)
+    one, small = (C.c_double * 2)(1.0, 0.0), (C.c_double * 2)(1e-3, 0.0)
+    t32 = lambda x: torch.as_tensor(np.ascontiguousarray(x, np.int32)).cuda()
+    # the whole pattern in random order; entry i's window is block i of a packed source
+    rr, cc = np.nonzero(mask)
+    perm = rng.permutation(len(rr))
+    rows, cols, n = t32(rr[perm]), t32(cc[perm]), len(rr)
+    off = torch.arange(n, dtype=torch.int64, device="cuda") * (b * b)
+    src = torch.rand(n * b * b, dtype=torch.float64, device="cuda") - 0.5
+    out = torch.empty(n * b * b, dtype=torch.float64, device="cuda")
+    found = torch.empty(n, dtype=torch.int32, device="cuda")
+    put = lambda alpha, summation: check(E.L.dbcsr_amd_bcsr_put_blocks(E.h, f64, C.byref(a), n, rows.data_ptr(), cols.data_ptr(), off.data_ptr(),
+                                                                       src.data_ptr(), alpha, summation, st.ptr))
+    get = lambda: check(E.L.dbcsr_amd_bcsr_get_blocks(E.h, f64, C.byref(a), n, rows.data_ptr(), cols.data_ptr(), off.data_ptr(), out.data_ptr(),
+                                                      found.data_ptr(), st.ptr))
+    # the general pair: B's pattern as a list in random order, reserved on A
+    gr, gc = np.nonzero(mask_b)
+    gperm = rng.permutation(len(gr))
+    g_rows, g_cols, g_n = t32(gr[gperm]), t32(gc[gperm]), len(gr)
+    nblk, nze, same, new, bad = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int64(), C.c_int64()
+    r_row_p, a_row_p, s_row_p, n_row_p = (torch.empty(nb + 1, dtype=torch.int32, device="cuda") for _ in range(4))
+    reserve_count = lambda: check(E.L.dbcsr_amd_bcsr_reserve_count(E.h, C.byref(ga), g_n, g_rows.data_ptr(), g_cols.data_ptr(), 0, r_row_p.data_ptr(),
+                                                                   C.byref(nblk), C.byref(nze), C.byref(new), C.byref(bad), st.ptr))
+    add_count = lambda: check(E.L.dbcsr_amd_bcsr_add_count(E.h, C.byref(ga), C.byref(gb), 0, a_row_p.data_ptr(), C.byref(nblk), C.byref(nze), C.byref(same),
+                                                           st.ptr))
+    result = lambda row_p: DbcsrMatrix(GA.row_blk_size, GA.col_blk_size, row_p, torch.empty(nblk.value, dtype=torch.int32, device="cuda"),
+                                       torch.empty(nblk.value, dtype=torch.int64, device="cuda"), torch.empty(nze.value, dtype=torch.float64, device="cuda"))
+    reserve_count()
+    union = int(np.count_nonzero((u < 2 * q) | mask_b))
+    if (new.value, bad.value, nblk.value) != (union - GA.nblks, 0, union):
+        sys.exit("the reserve count is wrong: nothing is timed")
+    RD = result(r_row_p)
+    rd = RD.desc(out=True)
+    add_count()
+    AD = result(a_row_p)
+    ad = AD.desc(out=True)
+
+    def reserve_general():
+        reserve_count()
+        check(E.L.dbcsr_amd_bcsr_reserve_apply(E.h, f64, C.byref(ga), C.byref(rd), st.ptr))
+
+    def add_general():
+        add_count()
+        check(E.L.dbcsr_amd_bcsr_add_apply(E.h, f64, one, C.byref(ga), small, C.byref(gb), C.byref(ad), st.ptr))
+
+    def reserve_none():
+        check(E.L.dbcsr_amd_bcsr_reserve_count(E.h, C.byref(a), n, rows.data_ptr(), cols.data_ptr(), 0, n_row_p.data_ptr(), C.byref(nblk), C.byref(nze),
+                                               C.byref(new), C.byref(bad), st.ptr))
+        assert new.value == 0 and bad.value == 0
+
+    def add_count_same():
+        check(E.L.dbcsr_amd_bcsr_add_count(E.h, C.byref(a), C.byref(b_), 0, s_row_p.data_ptr(), C.byref(nblk), C.byref(nze), C.byref(same), st.ptr))
+        assert same.value == 1
+
+    def add_flat():
+        assert dbcsr_add(A, B, 1.0, 1e-3, engine=E) is True
+
+    # what is timed is right: a sample of the blocks of each result against torch (the whole comparison is the tests' business)
+    pick = torch.as_tensor(rng.permutation(n)[:4096]).cuda()
+    where = torch.as_tensor(perm).cuda()[pick]   # (entry i names block perm[i] of the index: np.nonzero lists the pattern in index order)
+    put(one, 0)
+    get()
+    torch.cuda.synchronize()
+    if not torch.equal(A.data.view(-1, b * b)[where], src.view(-1, b * b)[pick]) or not torch.equal(out, src) or not bool(found.all()):
+        sys.exit("put or get is wrong: nothing is timed")
+    keep = A.data.view(-1, b * b)[where].clone()
+    put(one, 1)
+    torch.cuda.synchronize()
+    if not torch.equal(A.data.view(-1, b * b)[where], keep + src.view(-1, b * b)[pick]):
+        sys.exit("put with summation is wrong: nothing is timed")
+    del keep
+    reserve_general()
+    add_general()
+    torch.cuda.synchronize()
+    if not (torch.equal(RD.row_p, AD.row_p) and torch.equal(RD.col_i, AD.col_i) and torch.equal(RD.blk_p, AD.blk_p)):
+        sys.exit("the reserved pattern is not the union the add forms: nothing is timed")
+    run = {
+        "put.over": lambda: put(one, 0),
+        "get": get,
+        "copy_onto": lambda: check(E.L.dbcsr_amd_bcsr_copy_onto(E.h, f64, C.byref(b_), C.byref(a), st.ptr)),
+        "torch.copy_": lambda: A.data.copy_(B.data),
+        "put.sum": lambda: put(one, 1),
+        "add.flat": add_flat,
+        "put.python": lambda: dbcsr_put_blocks(A, rows, cols, src, off, keep_sparsity=True, engine=E),
+        "reserve.general": reserve_general,
+        "reserve.count": reserve_count,
+        "add.general": add_general,
+        "add.count": add_count,
+        "reserve.none": reserve_none,
+        "add.count.same": add_count_same,
+    }
+    nbytes = {"put.over": 16 * A.nze, "get": 16 * A.nze, "copy_onto": 16 * A.nze, "torch.copy_": 16 * A.nze, "put.sum": 24 * A.nze, "add.flat": 24 * A.nze,
+              "put.python": 16 * A.nze, "reserve.general": 8 * (GA.nze + RD.nze), "reserve.count": 0, "add.general": 8 * (GA.nze + GB.nze + AD.nze),
+              "add.count": 0, "reserve.none": 0, "add.count.same": 0}
+    times = {k: [] for k in run}
+    for step in range(args.warmup + args.alternations):
+        for k in run:
+            if k in ("put.sum", "add.flat"):
+                A.data.copy_(B.data)   # (values of the usual size for what follows: the sums before grew them)
+            t = sample(run[k], args.reps)
+            if step >= args.warmup:
+                times[k].append(t)
+    # a whole matrix from the list, against from_host of the same matrix: one call per sample, by the host's clock
+    sizes = A.row_blk_size
+    host = [x.cpu().numpy() for x in (sizes, sizes, A.row_p, A.col_i, A.blk_p, A.data)]
+    made = {"create": lambda: dbcsr_create_from_blocks(sizes, sizes, rows, cols, src, off, summation=True, engine=E),
+            "from_host": lambda: DbcsrMatrix.from_host(*host)}
+    M = made["create"]()
+    torch.cuda.synchronize()
+    if M.nblks != n or not torch.equal(M.col_i, A.col_i) or not torch.equal(M.data.view(-1, b * b)[where], src.view(-1, b * b)[pick]):
+        sys.exit("create_from_blocks is wrong: nothing is timed")
+    del M
+    for k in made:
+        times[k] = []
+    for step in range(args.warmup + args.alternations):
+        for k in made:
+            t = sample_wall(made[k], 1)
+            if step >= args.warmup:
+                times[k].append(t)
+    nbytes.update({"create": 16 * A.nze, "from_host": 8 * A.nze})
+    say("")
+    say("full pattern: %d blocks in a list in random order, %.1f MB per matrix and source; general: %d blocks, a list of %d, %d of them new (%.1f MB in, %.1f MB out)"
+        % (n, 8e-6 * A.nze, GA.nblks, g_n, RD.nblks - GA.nblks, 8e-6 * GA.nze, 8e-6 * RD.nze))
+    med = {}
+    for k in times:
+        v = sorted(times[k])
+        med[k] = v[len(v) // 2]
+        rate = ("%8.1f GB/s" % (1e-6 * nbytes[k] / med[k])) if nbytes[k] else "   (no data moved)"
+        say("  %-15s  median %9.4f ms  min %9.4f  max %9.4f  spread %5.1f %%  %s   samples: %s"
+            % (k, med[k], v[0], v[-1], 100 * (v[-1] - v[0]) / med[k], rate, " ".join("%.4f" % x for x in times[k])))
+    say("  (GB/s of reserve.general: A's blocks read and the result written; of create: the source read and the matrix written -- its zeros are written first;")
+    say("   of from_host: the data area copied once; create and from_host by the host's clock, one call per sample)")
+    say("")
+    say("time against the yardstick of the same run (median / median; the ratio per alternation, sample by sample)")
+    for k, y in (("put.over", "copy_onto"), ("put.over", "torch.copy_"), ("put.python", "put.over"), ("put.sum", "add.flat"), ("get", "copy_onto"),
+                 ("get", "torch.copy_"), ("reserve.general", "add.general"), ("reserve.count", "add.count"), ("reserve.none", "add.count.same"),
+                 ("create", "from_host")):
+        r = sorted(x / z for x, z in zip(times[k], times[y]))
+        say("  %-15s / %-14s  %.2f   (per alternation %.2f ... %.2f)" % (k, y, med[k] / med[y], r[0], r[-1]))
+    r_apply, a_apply = med["reserve.general"] - med["reserve.count"], med["add.general"] - med["add.count"]
+    say("  apply = general - count: reserve %.4f ms (%.1f GB/s), add %.4f ms (%.1f GB/s)"
+        % (r_apply, 1e-6 * nbytes["reserve.general"] / r_apply, a_apply, 1e-6 * nbytes["add.general"] / a_apply))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=32768)
@@ -790,6 +961,7 @@ def main():
     ap.add_argument("--dense", action="store_true", help="only the dense conversion: to_dense, from_dense, create_from_dense and what they replace")
     ap.add_argument("--submatrix", action="store_true", help="only the submatrix method: gather, scatter, and the full-set gather against to_dense")
     ap.add_argument("--elementwise", action="store_true", help="only the element-wise operations on two patterns and their yardsticks")
+    ap.add_argument("--blocks", action="store_true", help="only the block lists: reserve, put, get, create_from_blocks and their yardsticks")
     ap.add_argument("--mfma-tflops", type=float, default=None, help="with --rank-update / --block-scale: the fp64 MFMA figure bench.py --full measured in the same session")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     args = ap.parse_args()
@@ -818,6 +990,8 @@ def main():
         return submatrix(args, say, lines, rng)
     if args.elementwise:
         return elementwise(args, say, lines, rng, b, nb, st)
+    if args.blocks:
+        return blocks(args, say, lines, rng, b, nb, st)
     only =("norm", "norm.T", "matvec.N", "matvec.T", "matvec.S", "gersh.N", "colnorm", "gersh.S") if args.matvec else None
     # the same-pattern pair
     mask = rng.random((nb, nb)) < args.fill_flat
