@@ -17,6 +17,7 @@ from .operations import (dbcsr_func_artanh, dbcsr_func_asin, dbcsr_func_cos, dbc
                          dbcsr_func_ddtanh, dbcsr_func_dsin, dbcsr_func_dtanh, dbcsr_func_inverse, dbcsr_func_sin, dbcsr_func_tanh)
 from .operations import (dbcsr_create_from_blocks, dbcsr_get_blocks, dbcsr_put_blocks, dbcsr_reserve_all_blocks,  # noqa: F401
                          dbcsr_reserve_blocks, dbcsr_reserve_diag_blocks)
+from .csr import dbcsr_create_from_csr, dbcsr_csr_to_torch, dbcsr_from_csr, dbcsr_to_csr  # noqa: F401
 from .submatrix import SubmatrixPlan, dbcsr_submatrix_apply, dbcsr_submatrix_gather, dbcsr_submatrix_plan, dbcsr_submatrix_scatter  # noqa: F401
 
 __all__ = ["load_library", "library_path", "dbcsr_add", "dbcsr_scale", "dbcsr_add_on_diag", "dbcsr_trace", "dbcsr_dot", "dbcsr_frobenius_norm",
@@ -28,4 +29,5 @@ __all__ = ["load_library", "library_path", "dbcsr_add", "dbcsr_scale", "dbcsr_ad
            "dbcsr_func_dcos", "dbcsr_func_ddcos",
            "dbcsr_reserve_blocks", "dbcsr_put_blocks", "dbcsr_get_blocks", "dbcsr_reserve_diag_blocks", "dbcsr_reserve_all_blocks",
            "dbcsr_create_from_blocks",
+           "dbcsr_to_csr", "dbcsr_from_csr", "dbcsr_create_from_csr", "dbcsr_csr_to_torch",
            "SubmatrixPlan", "dbcsr_submatrix_plan", "dbcsr_submatrix_gather", "dbcsr_submatrix_scatter", "dbcsr_submatrix_apply"]

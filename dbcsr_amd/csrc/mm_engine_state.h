@@ -178,6 +178,33 @@ struct Engine {
   int rsv_nblkrows = 0, rsv_nblkcols = 0;
   int64_t rsv_nblks_a = 0, rsv_nblks = 0, rsv_nze = 0;
 
+  // ---- element CSR (mm_engine_csr.h): what dbcsr_amd_bcsr_to_csr_count leaves for its _apply, in buffers and fields that no other entry writes -- an
+  // add, a norm, a put or a multiply between the two halves changes nothing here, and these change nothing of theirs ----
+  DevBuf<int64_t> csr_off;    // of the counted matrix: roff[nblkrows + 1], coff[nblkcols + 1], base[nblkrows + 1] (the first slot of every block row)
+  DevBuf<int64_t> csr_pos;    // pos[nslots + 1]: the CSR position of every row piece, the total behind them
+  DevBuf<int> csr_slots;      // slots[nslots]: the kept elements of every row piece
+  DevBuf<int> csr_rows;       // the slots of every block row [nblkrows]: what base is the scan of
+  DevBuf<int64_t> csr_aux;    // _from_csr and _csr_name_blocks: roff, coff of their block sizes (nothing is pending in it)
+  bool csr_pending = false;   // a dbcsr_amd_bcsr_to_csr_count succeeded and no _apply has served it
+  const void *csr_row_p = nullptr, *csr_rs = nullptr, *csr_cs = nullptr;   // ... for the matrix with this row_p, these size arrays,
+  int csr_nblkrows = 0, csr_nblkcols = 0, csr_datatype = 0, csr_use_eps = 0;   // these counts, this type and this filter
+  int64_t csr_nblks = 0, csr_nnz = 0, csr_nslots = 0;
+  double csr_eps = 0.0;
+  // the slot count of an index (and its element count, the nnz without eps), which only the device knows: remembered per index as alg_len remembers
+  // the lengths (same row_p and size arrays, same non-zero index_stamp), fetched otherwise -- then, and only then, a count synchronises for them
+  struct CsrLen {
+    const void* row_p = nullptr;
+    const void* rs = nullptr;
+    const void* cs = nullptr;
+    uint64_t stamp = 0;
+    int nbr = 0, nbc = 0;
+    int64_t nblks = 0, nslots = 0;
+    int64_t nze = -1;   // the elements the index names, where a count without eps fetched them (-1: not known)
+  };
+  static constexpr int kCsrLens = 8;
+  CsrLen csr_len[kCsrLens];
+  int csr_len_next = 0;
+
   // ---- switches (mm_engine_env.h) ----
   Switches sw;      // the numeric phase's kernel families (mm_choose.h)
   LabSwitches lab;  // lab build only: no state in the shipping build

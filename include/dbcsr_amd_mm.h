@@ -633,6 +633,44 @@ int dbcsr_amd_bcsr_put_blocks(void* handle, libsmm_acc_data_t datatype, dbcsr_am
 int dbcsr_amd_bcsr_get_blocks(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, int64_t n, const int32_t* rows, const int32_t* cols,
   const int64_t* dst_off, void* dst, int32_t* found, void* stream);
 
+/* Element CSR: the reference's conversion between a matrix and the element-wise CSR form (src/ops/dbcsr_csr_conversions.F: dbcsr_csr_create_from_dbcsr,
+ * dbcsr_convert_dbcsr_to_csr, dbcsr_convert_csr_to_dbcsr, dbcsr_to_csr_filter; what CP2K hands to PEXSI and writes with KS_CSR_WRITE), without leaving
+ * the device.  The reference's source could not be consulted: the rule of the eps filter stated below is the semantics of this library.  The CSR form of
+ * this library: crow[n_rows + 1] int64 with crow[0] = 0 (positions pass 2^31 on matrices that fit one GPU), col[nnz] int32, 0-based element columns
+ * ascending inside a row, values[nnz] of the matrix' type; all three on the device.  Same types as the algebra above (-10 for another type code).  -1 for a
+ * null handle, matrix or array, negative sizes, and more than 2^31 - 1 element columns; 0 with nothing but crow written for a matrix without blocks.  The
+ * index is served as it is: a stored triangle is not expanded (dbcsr_amd_bcsr_desymmetrized does that first).  Everything goes by the index: the holes of
+ * an unpacked matrix are never read or written.  All four work in buffers of their own (and the scan's scratch): no saved plan is touched, no work area of
+ * the symbolic phase is written.  No atomics on data; the same bits on every call; every offset into the data area, col and values is formed in 64 bits.
+ *   _to_csr_count  writes crow [n_rows + 1] (device) and *nnz (host).  use_eps == 0: every element the index names is an entry -- crow and *nnz come from
+ *     the index alone and NO element of the data area is read (m->data may point anywhere).  use_eps != 0 (eps >= 0; negative or NaN: -1): an element is
+ *     DROPPED iff |x| <= eps -- real types compare in their own precision, complex ones hypot(re, im) in double -- so eps = 0 drops exactly +-0 and a NaN
+ *     stays.  Synchronises once, for *nnz; once more when it meets an index it does not know (same row_p and size arrays, same non-zero index_stamp), for
+ *     the number of row pieces it works on, as _to_dense does for the lengths; with use_eps == 0 and a known index it synchronises nothing.  -1 also for
+ *     more than 2^31 - 9 row pieces (element rows times stored blocks of their block row, summed).
+ *   _to_csr_apply  fills col and values [nnz], bit for bit.  Asynchronous on stream.  One _apply per _count: an _apply without a pending _count, a second
+ *     one, or one for a matrix other than the counted one (row_p, the size arrays, the block counts, the type) is refused (-1) and writes nothing.  What is
+ *     pending lives in fields and buffers of its own: an add, a norm, a put or a multiply between the two halves does not disturb it and is not
+ *     disturbed by it.  With eps the data area must be the counted one; one that changed gives wrong entries, never a store outside col / values[0, nnz).
+ *   _from_csr      the mirror of _from_dense_apply: every element of every block the index of m names is written exactly once -- the CSR value at its
+ *     (row, column), or +0.0 where the CSR has none -- and nothing else: no index array, no hole of an unpacked matrix.  CSR entries whose block m does not
+ *     store are ignored, as are entries with a column outside [0, n_cols).  Contract: columns ascend strictly inside a row (what _to_csr_apply and
+ *     torch's to_sparse_csr() produce); a CSR that breaks it gives wrong values, never an access outside col / values[0, nnz) -- every position formed
+ *     from crow is clamped -- or outside the blocks.  -1 for n_rows / n_cols that are not the sums of the block sizes (remembered per set of block sizes
+ *     as _to_dense remembers them: one synchronisation the first time, none afterwards).  No symmetry is applied.  The norms a numeric phase announced
+ *     are forgotten.  Asynchronous on stream.
+ *   _csr_name_blocks  rows[t], cols[t] (int32 [nnz], device) <- the block (R, C) of the structure row_blk_size [nblkrows] x col_blk_size [nblkcols] (device)
+ *     that holds CSR entry t, found by binary searches in the running sums of the block sizes; (-1, -1) for an entry outside the structure (or one that
+ *     no row of crow[0 ... n_rows] covers), which _reserve_count then reports as invalid.  The list is what _reserve_count takes to build the pattern of
+ *     "a new matrix of the blocks that hold at least one CSR entry".  Asynchronous on stream. */
+int dbcsr_amd_bcsr_to_csr_count(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, int use_eps, double eps, int64_t* crow, int64_t* nnz,
+  void* stream);
+int dbcsr_amd_bcsr_to_csr_apply(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* m, int32_t* col, void* values, void* stream);
+int dbcsr_amd_bcsr_from_csr(void* handle, libsmm_acc_data_t datatype, int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t* crow, const int32_t* col,
+  const void* values, dbcsr_amd_bcsr* m, void* stream);
+int dbcsr_amd_bcsr_csr_name_blocks(void* handle, int64_t n_rows, int64_t nnz, const int64_t* crow, const int32_t* col, const int32_t* row_blk_size,
+  const int32_t* col_blk_size, int nblkrows, int nblkcols, int32_t* rows, int32_t* cols, void* stream);
+
 /* Measurement helper (bench.py, roofline.fabric): what the L2 <-> Infinity-Cache fabric of the current device delivers, in TB/s -- a
  * plain streaming read of a 160 MB window by all CUs, and the block gather of the block-product dataflow (4232-byte blocks from
  * pseudo-random places of the window into LDS, whole 128-byte lines counted).  Takes well under a second; synchronises the device. */

@@ -81,6 +81,15 @@ one call per sample) against dbcsr_to_dense timed the same way.  The condition: 
 
     python tools/ops_bench.py --dense --alternations 7 --warmup 2 --out profiles/dense_conversion.txt
 
+With --csr only the element CSR form is timed (dbcsr_to_csr, dbcsr_from_csr, dbcsr_create_from_csr; kernels of dbcsr_amd/csrc/mm_csr.h) on the matrix of
+--dense (float64, 504 x 504 blocks of 23 x 23, every block stored and one block in ten), alternating: to_csr without eps and with an eps that drops about
+half of the elements (a wall-clock row: it answers on the host), from_csr onto the same pattern, create_from_csr (wall clock, one call per sample), and the
+yardsticks copy_ of the data area, dbcsr_to_dense of the same matrix, dbcsr_to_dense(...).to_sparse_csr() on the device where torch offers it (said
+otherwise), and the host round trip the feature replaces (to_host, a numpy loop over the blocks, upload, synchronise; wall clock, one call per sample)
+against dbcsr_to_csr timed the same way.  The condition: the device path is faster than the host round trip in every alternation:
+
+    python tools/ops_bench.py --csr --alternations 7 --warmup 2 --out profiles/csr_conversion.txt
+
 With --submatrix only the submatrix method's two copies are timed (dbcsr_submatrix_gather, dbcsr_submatrix_scatter; kernels of
 dbcsr_amd/csrc/mm_submatrix.h) on the matrix of --dense at one block in ten: with one submatrix per block column, gather into the whole batch padded to
 the largest side, scatter out of it, and zero_() of the batch as the floor of writing it; and the full-set gather (one submatrix holding every block
@@ -605,6 +614,117 @@ def dense_conversion(args, say, lines, rng):
             f.write("\n".join(lines) + "\n")
 
 
+def host_csr(rs, cs, row_p, col_i, blk_p, data):
+    """the element CSR of a host matrix by a loop over its blocks (numpy per block: the transposed block into the rows of its block row)"""
+    ro, co = np.concatenate([[0], np.cumsum(rs, dtype=np.int64)]), np.concatenate([[0], np.cumsum(cs, dtype=np.int64)])
+    crow = np.zeros(int(ro[-1]) + 1, np.int64)
+    cols, vals = [], []
+    for r in range(len(rs)):
+        m, blocks = int(rs[r]), range(int(row_p[r]), int(row_p[r + 1]))
+        if not len(blocks):
+            continue
+        tiles = [data[blk_p[b]:blk_p[b] + m * int(cs[col_i[b]])].reshape(int(cs[col_i[b]]), m).T for b in blocks]
+        line = np.concatenate([np.arange(co[col_i[b]], co[col_i[b] + 1], dtype=np.int32) for b in blocks])
+        vals.append(np.concatenate(tiles, axis=1).reshape(-1))
+        cols.append(np.tile(line, m))
+        crow[ro[r] + 1:ro[r + 1] + 1] = line.size
+    crow = np.cumsum(crow)
+    return crow, (np.concatenate(cols) if cols else np.zeros(0, np.int32)), (np.concatenate(vals) if vals else np.zeros(0, data.dtype))
+
+
+def csr_conversion(args, say, lines, rng):
+    from dbcsr_amd.csr import dbcsr_create_from_csr, dbcsr_from_csr, dbcsr_to_csr
+    E = MultiplyEngine()
+    b, nb = 23, 504
+    n = b * nb
+    results = {}
+    out_r = torch.empty((n, n), dtype=torch.float64, device="cuda")
+    eps = 0.25   # (uniform(-0.5, 0.5) values: about half of them are dropped)
+    for fill in (1.0, 0.1):
+        M = matrix_of(rng.random((nb, nb)) < fill, b, 40)
+        X = M.copy()
+        # what is timed is right: against the host's block loop, bit for bit (the whole comparison is the tests' business)
+        ref = host_csr(*M.to_host())
+        got = dbcsr_to_csr(M, engine=E)
+        if any(g.cpu().numpy().tobytes() != r.tobytes() for g, r in zip(got, ref)):
+            sys.exit("dbcsr_to_csr is wrong: nothing is timed")
+        X.data.fill_(float("nan"))
+        dbcsr_from_csr(*got, X, engine=E)
+        if X.data.cpu().numpy().tobytes() != M.data.cpu().numpy().tobytes():
+            sys.exit("dbcsr_from_csr is wrong: nothing is timed")
+        half = dbcsr_to_csr(M, eps=eps, engine=E)
+        keep = np.abs(ref[2]) > eps
+        if half[2].cpu().numpy().tobytes() != ref[2][keep].tobytes() or half[1].cpu().numpy().tobytes() != ref[1][keep].tobytes():
+            sys.exit("dbcsr_to_csr(eps) is wrong: nothing is timed")
+        kept = float(keep.mean())
+        del ref, half, keep
+        crow, col, values = got
+
+        def host_round_trip():
+            out = [torch.as_tensor(a).cuda() for a in host_csr(*M.to_host())]
+            torch.cuda.synchronize()
+            return out
+
+        def torch_csr():
+            return dbcsr_to_dense(M, out=out_r, engine=E).to_sparse_csr()
+
+        run = {
+            "copy": lambda: X.data.copy_(M.data),
+            "to_dense": lambda: dbcsr_to_dense(M, out=out_r, engine=E),
+            "to_csr": lambda: dbcsr_to_csr(M, engine=E),
+            "to_csr(eps)": lambda: dbcsr_to_csr(M, eps=eps, engine=E),
+            "from_csr": lambda: dbcsr_from_csr(crow, col, values, X, engine=E),
+            "create": lambda: dbcsr_create_from_csr(crow, col, values, M.row_blk_size, M.col_blk_size, engine=E),
+            "torch.csr": torch_csr,
+            "device path": lambda: dbcsr_to_csr(M, engine=E),
+            "host path": host_round_trip,
+        }
+        try:
+            torch_csr()
+            torch.cuda.synchronize()
+            torch_note = None
+        except Exception as e:   # (what torch-ROCm does not offer is reported, not timed)
+            torch_note = "%s: %s" % (type(e).__name__, str(e).splitlines()[0] if str(e) else "")
+            del run["torch.csr"]
+        wall = ("to_csr(eps)", "create", "torch.csr", "device path", "host path")
+        times = {k: [] for k in run}
+        for step in range(args.warmup + args.alternations):
+            for k in run:
+                x = sample_wall(run[k], 1 if k in ("host path", "create", "torch.csr") else args.reps) if k in wall else sample(run[k], args.reps)
+                if step >= args.warmup:
+                    times[k].append(x)
+        say("")
+        say("%d x %d blocks of %d x %d, fill %.2f: %d blocks, %.1f MB of blocks = nnz %d; eps = %.2f keeps %.1f %% of the elements"
+            % (nb, nb, b, b, fill, M.nblks, 8e-6 * M.nze, M.nze, eps, 100 * kept))
+        if torch_note:
+            say("  torch.csr (dbcsr_to_dense(...).to_sparse_csr() on the device) is not offered here: %s" % torch_note)
+        med = {}
+        for k in run:
+            v = sorted(times[k])
+            med[k] = v[len(v) // 2]
+            # elements of 8 bytes read + written: the data area and values; col counts half an element per entry
+            moved = {"copy": 2 * M.nze, "to_dense": n * n + M.nze, "to_csr": 2.5 * M.nze, "from_csr": 2.5 * M.nze}.get(k)
+            say("  %-16s median %10.4f ms  min %10.4f  max %10.4f  spread %5.1f %%  %s   samples: %s"
+                % (k, med[k], v[0], v[-1], 100 * (v[-1] - v[0]) / med[k], "%8.1f GB/s" % (8e-6 * moved / med[k]) if moved else " " * 13,
+                   " ".join("%.4f" % x for x in times[k])))
+        say("  ratios (median / median): to_csr / copy %.2f, to_csr / to_dense %.2f, to_csr(eps) / to_csr %.2f, from_csr / copy %.2f, create / from_csr %.2f%s"
+            % (med["to_csr"] / med["copy"], med["to_csr"] / med["to_dense"], med["to_csr(eps)"] / med["to_csr"], med["from_csr"] / med["copy"],
+               med["create"] / med["from_csr"], ", to_csr / torch.csr %.3f" % (med["to_csr"] / med["torch.csr"]) if "torch.csr" in med else ""))
+        results[fill] = times
+        del M, X, got, crow, col, values
+    say("")
+    say("condition: the device path (dbcsr_to_csr, allocation included, synchronised) is faster than the host round trip in every alternation")
+    ok = True
+    for fill, times in results.items():
+        r = sorted(x / z for x, z in zip(times["device path"], times["host path"]))
+        ok = ok and r[-1] < 1.0
+        say("  fill %.2f: device path / host path  %.6f ... %.6f   %s" % (fill, r[0], r[-1], "holds" if r[-1] < 1.0 else "FAILS"))
+    say("  the condition %s" % ("holds" if ok else "FAILS"))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def submatrix(args, say, lines, rng):
     """the submatrix method's two copies on the matrix of the dense conversion, and the full-set gather against dbcsr_to_dense"""
     E = MultiplyEngine()
@@ -959,6 +1079,7 @@ def main():
     ap.add_argument("--block-inverse", action="store_true", help="only the block diagonal: get_block_diag, invert_block_diag and what they replace")
     ap.add_argument("--block-scale", action="store_true", help="only the block diagonal applied to a matrix: left, right, both, dbcsr_scale and the multiply it replaces")
     ap.add_argument("--dense", action="store_true", help="only the dense conversion: to_dense, from_dense, create_from_dense and what they replace")
+    ap.add_argument("--csr", action="store_true", help="only the element CSR form: to_csr, from_csr, create_from_csr and what they replace")
     ap.add_argument("--submatrix", action="store_true", help="only the submatrix method: gather, scatter, and the full-set gather against to_dense")
     ap.add_argument("--elementwise", action="store_true", help="only the element-wise operations on two patterns and their yardsticks")
     ap.add_argument("--blocks", action="store_true", help="only the block lists: reserve, put, get, create_from_blocks and their yardsticks")
@@ -986,6 +1107,8 @@ def main():
         return block_scale(args, say, lines, rng)
     if args.dense:
         return dense_conversion(args, say, lines, rng)
+    if args.csr:
+        return csr_conversion(args, say, lines, rng)
     if args.submatrix:
         return submatrix(args, say, lines, rng)
     if args.elementwise:
