@@ -1,10 +1,12 @@
 """Blocks of 33 ... 80 (libsmm_acc's range: max_kernel_dim = 80, src/core/dbcsr_config.F:185; libsmm_acc.cpp:324-339) -- round 6: 33 ... 40 in
 both dimensions through the one-wave kernel mm_numeric_f64_mid (see CASES), the rest through the
 workgroup-per-C-block kernel mm_numeric_f64_big (one 2 x 2 arrangement of waves per block, operand slabs of 16 inner indices shared
-through LDS) against the CPU oracle: every sub-block shape TM x TN in {2 .. 5}^2 that the host can choose, inner dimensions with every
+through LDS) against the CPU oracle: the sub-block shapes TM x TN <2,2> <2,5> <3,3> <3,4> <3,5> <4,4> <5,2> <5,3> <5,5> of the workgroup kernel
+and the slab shapes <9,9> <9,10> <10,9> <10,10> <9,12> <11,11> <11,12> <12,12> at sizes of tens of blocks per dimension, inner dimensions with every
 remainder modulo 4 and 16 (slab and k-step tails), blocks smaller than the launch's largest in the same launch, C blocks without
-products, alpha / beta, retain_sparsity with in-place accumulation, transposes, a filtered multiply.  Index bit-exact, flop equal,
-values 1e-10 relative -- the bar of the whole suite."""
+products, alpha / beta, retain_sparsity and a second product on the retained pattern, transposes, a filtered multiply.  Index bit-exact, flop equal,
+values 1e-10 relative -- the bar of the whole suite.  The other instances -- all 16 pairs of {2 .. 5}^2 and all 43 slab shapes -- run once each on
+small matrices in tests/test_gpu_kernel_instances.py (rows: tests/kernel_instances.py)."""
 import numpy as np
 import pytest
 import torch

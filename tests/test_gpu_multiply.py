@@ -12,6 +12,7 @@ import torch
 from dbcsr_amd.multiply import MultiplyEngine, dbcsr_multiply
 from oracle import oracle as O
 from tests.gpu_util import dev_to_bcsr, rel_err, to_dev
+from tests.test_numeric_choice import F32_EXACT_CUBES
 
 pytestmark = pytest.mark.gpu
 
@@ -264,17 +265,24 @@ def test_k_chunked_passes_reuse_their_views_and_plans():
 
 
 @pytest.mark.parametrize("size", list(range(9, 33)))
-def test_exact_size_kernels_every_cube_with_tails(size):
+def test_exact_size_kernels_every_cube_with_tails(monkeypatch, size):
     """Uniform size s (one exact-size kernel per cube 9..32) with a ragged tail block in every dimension: the tail row / column /
-    inner blocks take the fall-back paths inside the same launch.  fp64 at 1e-10, fp32 against the fp64 oracle at 1e-5."""
+    inner blocks take the fall-back paths inside the same launch.  fp64 at 1e-10, fp32 against the fp64 oracle at 1e-5; the fp32 half on an engine
+    of its own, whose kernel is the one tests/test_numeric_choice.py expects for the case (direct form for 16 / 24 / 32)."""
+    _, case, expect = F32_EXACT_CUBES[size - 9]
     dim = 12 * size + max(1, size // 3)
-    A, B, Cm = O.perf_case(dim, dim, dim, 0.6, 0.6, 0.7, [1, size], [1, size], [1, size])
+    assert case == (dim, dim, dim, 0.6, 0.6, 0.7, [1, size], [1, size], [1, size])
+    A, B, Cm = O.perf_case(*case)
     check_against_oracle(A, B, Cm, alpha=0.75, beta=-1.25)
     ref, info = O.multiply("N", "N", 0.75, A, B, -1.25, Cm)
     f32 = lambda M: O.Bcsr(M.row_sizes, M.col_sizes, M.row_p, M.col_i, M.blk_p, M.data.astype(np.float32))
     dA, dB, dC = to_dev(f32(A)), to_dev(f32(B)), to_dev(f32(Cm))
-    dbcsr_multiply("N", "N", 0.75, dA, dB, -1.25, dC)
+    for k in [k for k in os.environ if k.startswith("DBCSR_AMD_MM_")]:
+        monkeypatch.delenv(k)
+    eng = MultiplyEngine()
+    dbcsr_multiply("N", "N", 0.75, dA, dB, -1.25, dC, engine=eng)
     torch.cuda.synchronize()
+    assert eng.last_kernel() == expect == "mm_numeric_f32_%s<%d,%d,%d>" % ("direct" if size in (16, 24, 32) else "hot", size, size, size)
     out = dev_to_bcsr(dC)
     assert np.array_equal(out.row_p, ref.row_p) and np.array_equal(out.col_i, ref.col_i) and np.array_equal(out.blk_p, ref.blk_p)
     assert float(np.max(np.abs(out.data - ref.data))) <= 1e-5 * float(np.max(np.abs(ref.data)))

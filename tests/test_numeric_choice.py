@@ -209,6 +209,18 @@ F32_VARIANTS = [
 ]
 
 
+
+
+# tests/test_gpu_multiply.py: test_exact_size_kernels_every_cube_with_tails -- every cube of 9 ... 32 with a ragged tail block in every dimension (twelve blocks
+# of the size and the tail: the size dominates); the fp32 half takes the direct form where k is a multiple of 8, else the form that stages both operands
+def exact_cube_with_tails(size):
+    dim = 12 * size + max(1, size // 3)
+    return (dim, dim, dim, 0.6, 0.6, 0.7, [1, size], [1, size], [1, size])
+
+
+F32_EXACT_CUBES = [({}, exact_cube_with_tails(s), "mm_numeric_f32_%s<%d,%d,%d>" % ("direct" if s in (16, 24, 32) else "hot", s, s, s)) for s in range(9, 33)]
+
+
 @pytest.mark.parametrize("env,case,expect", VARIANTS)
 def test_fp64_kernel_variants(shims, env, case, expect):
     name, _ = choose(shims, env, case, products_per_block=PPB.get(id(case), 10.0))
@@ -219,6 +231,13 @@ def test_fp64_kernel_variants(shims, env, case, expect):
 def test_fp32_kernel_variants(shims, env, case, expect):
     name, _ = choose(shims, env, case, fp64=False)
     assert name.startswith(expect), (name, expect)
+
+
+@pytest.mark.parametrize("env,case,expect", F32_EXACT_CUBES, ids=[str(s) for s in range(9, 33)])
+def test_fp32_exact_size_kernel_of_every_cube(shims, env, case, expect):
+    assert choose(shims, env, case, fp64=False)[0] == expect
+    size = case[6][1]
+    assert choose(shims, env, case)[0] == "mm_numeric_f64_hot<%d,%d,%d>" % (size, size, size)   # (the fp64 half of the same test)
 
 
 def test_fp32_group_automatic_choice(shims):
