@@ -19,6 +19,8 @@ from .operations import (dbcsr_create_from_blocks, dbcsr_get_blocks, dbcsr_put_b
                          dbcsr_reserve_blocks, dbcsr_reserve_diag_blocks)
 from .csr import dbcsr_create_from_csr, dbcsr_csr_to_torch, dbcsr_from_csr, dbcsr_to_csr  # noqa: F401
 from .submatrix import SubmatrixPlan, dbcsr_submatrix_apply, dbcsr_submatrix_gather, dbcsr_submatrix_plan, dbcsr_submatrix_scatter  # noqa: F401
+from .tensor import (DbcsrTensor, dbcsr_t_block_indices, dbcsr_t_contract, dbcsr_t_copy, dbcsr_t_copy_matrix_to_tensor,  # noqa: F401
+                     dbcsr_t_copy_tensor_to_matrix, dbcsr_t_create, dbcsr_t_create_from_blocks, dbcsr_t_filter, dbcsr_t_get_blocks, dbcsr_t_put_blocks)
 
 __all__ = ["load_library", "library_path", "dbcsr_add", "dbcsr_scale", "dbcsr_add_on_diag", "dbcsr_trace", "dbcsr_dot", "dbcsr_frobenius_norm",
            "dbcsr_maxabs_norm", "dbcsr_gershgorin_norm", "dbcsr_norm", "dbcsr_norm_frobenius", "dbcsr_norm_maxabsnorm", "dbcsr_norm_gershgorin",
@@ -30,4 +32,6 @@ __all__ = ["load_library", "library_path", "dbcsr_add", "dbcsr_scale", "dbcsr_ad
            "dbcsr_reserve_blocks", "dbcsr_put_blocks", "dbcsr_get_blocks", "dbcsr_reserve_diag_blocks", "dbcsr_reserve_all_blocks",
            "dbcsr_create_from_blocks",
            "dbcsr_to_csr", "dbcsr_from_csr", "dbcsr_create_from_csr", "dbcsr_csr_to_torch",
-           "SubmatrixPlan", "dbcsr_submatrix_plan", "dbcsr_submatrix_gather", "dbcsr_submatrix_scatter", "dbcsr_submatrix_apply"]
+           "SubmatrixPlan", "dbcsr_submatrix_plan", "dbcsr_submatrix_gather", "dbcsr_submatrix_scatter", "dbcsr_submatrix_apply",
+           "DbcsrTensor", "dbcsr_t_create", "dbcsr_t_create_from_blocks", "dbcsr_t_block_indices", "dbcsr_t_put_blocks", "dbcsr_t_get_blocks", "dbcsr_t_copy",
+           "dbcsr_t_copy_matrix_to_tensor", "dbcsr_t_copy_tensor_to_matrix", "dbcsr_t_filter", "dbcsr_t_contract"]

@@ -142,6 +142,6 @@ int dbcsr_amd_bcsr_get_blocks(void* handle, libsmm_acc_data_t datatype, const db
   DBCSR_AMD_BY_TYPE(get_launch, st, m, n, rows, cols, dst_off, dst, found);
   return check(hipGetLastError(), "dbcsr_amd_bcsr_get_blocks", __FILE__, __LINE__);
 }
-// (DBCSR_AMD_BY_TYPE stays defined for mm_engine_csr.h, which follows this file and ends its life)
+// (DBCSR_AMD_BY_TYPE stays defined for mm_engine_csr.h and mm_engine_tensor.h, which follow this file; the last one ends its life)
 
 #endif

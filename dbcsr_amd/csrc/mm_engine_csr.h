@@ -1,5 +1,5 @@
-// mm_engine_csr.h -- part of mm_engine.hip (included inside extern "C", after mm_engine_blocklist.h; it uses the helpers of mm_engine_algebra.h and ends the
-// life of DBCSR_AMD_BY_TYPE): the C-ABI entries of the element CSR form -- dbcsr_amd_bcsr_to_csr_count / _to_csr_apply, dbcsr_amd_bcsr_from_csr and
+// mm_engine_csr.h -- part of mm_engine.hip (included inside extern "C", after mm_engine_blocklist.h; it uses the helpers of mm_engine_algebra.h): the
+// C-ABI entries of the element CSR form -- dbcsr_amd_bcsr_to_csr_count / _to_csr_apply, dbcsr_amd_bcsr_from_csr and
 // dbcsr_amd_bcsr_csr_name_blocks.  Kernels: mm_csr.h.  They work in Engine::csr_* and the scan's scratch alone: no work area of the symbolic phase is
 // touched and plan_invalidate is not called -- a multiply afterwards reuses its plan.  What a count leaves for its apply (the offsets of the block rows
 // and columns, the slot bases, the scanned positions) lives in csr_off / csr_pos, which no other entry writes: _from_csr and _csr_name_blocks scan their
@@ -184,6 +184,6 @@ int dbcsr_amd_bcsr_csr_name_blocks(void* handle, int64_t n_rows, int64_t nnz, co
     hipLaunchKernelGGL(csr_name_blocks, grid_for(n_rows * 64), dim3(256), 0, st, crow, col, nnz, n_rows, roff, coff, nblkrows, nblkcols, rows, cols);
   return check(hipGetLastError(), "dbcsr_amd_bcsr_csr_name_blocks", __FILE__, __LINE__);
 }
-#undef DBCSR_AMD_BY_TYPE
+// (DBCSR_AMD_BY_TYPE stays defined for mm_engine_tensor.h, which follows this file and ends its life)
 
 #endif

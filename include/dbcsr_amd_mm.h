@@ -671,6 +671,29 @@ int dbcsr_amd_bcsr_from_csr(void* handle, libsmm_acc_data_t datatype, int64_t n_
 int dbcsr_amd_bcsr_csr_name_blocks(void* handle, int64_t n_rows, int64_t nnz, const int64_t* crow, const int32_t* col, const int32_t* row_blk_size,
   const int32_t* col_blk_size, int nblkrows, int nblkcols, int32_t* rows, int32_t* cols, void* stream);
 
+/* Tensors: the one device primitive under the block-sparse tensor interface (dbcsr_amd/tensor.py, the dbcsr_t_* of the reference's src/tensors).  A tensor
+ * is stored as a matrix without symmetry: a mapping (map1 | map2) folds its dimensions into block rows and block columns, the first entry of each tuple
+ * running fastest, for the block index and inside a block alike; a stored block is the Fortran array of the tensor block with its dimensions in the order
+ * map1 ++ map2.  The reference's sources could not be consulted: the layout is the one stated here and in DESIGN 3.19, checked against dense numpy.
+ * Changing the mapping of a tensor -- and with it every contraction whose operands are not folded the way the multiply needs them -- is index work on
+ * nblks integers plus one move that permutes the inside of every block.  The move is this call; everything else is the matrix interface above.
+ *   _tensor_permute_blocks  moves a list of nblk blocks in one launch.  Entry b is the Fortran array of extents ext[4 b ... 4 b + 3] (int32, device; in the
+ *     order the source stores them; entries from `rank` on are not read and count as 1) at src + src_off[b]; it is written at dst + dst_off[b] with its
+ *     dimensions permuted: dimension j of the written array is dimension perm[j] of the read one (numpy.transpose's convention; perm: `rank` entries on
+ *     the HOST, one permutation for the whole launch).  Offsets are int64 ELEMENT offsets (device), src_len / dst_len the element counts of the two areas;
+ *     every address is formed in 64 bits.  Bit for bit: elements of 4, 8 or 16 bytes are loaded and stored, never computed with.  Every element of every
+ *     written window is written exactly once, nothing else of dst is written, src is never written.  An entry is skipped on the device as a whole -- not
+ *     read, not written -- when one of its windows does not lie inside [0, src_len) / [0, dst_len), when an extent is below 1, or when it has 2^31
+ *     elements or more (a block's element count is 32-bit everywhere in this library).  Written windows that overlap each other are the caller's error.
+ *     Dimensions that are adjacent on both sides in the same order are moved as one, extents of 1 drop out; what is left with the same fastest dimension
+ *     on both sides is copied in runs with 16-byte accesses aligned on the written side, anything else goes through a 32 x 33 LDS tile so that both
+ *     sides are walked along their contiguous direction.  No atomics, no scratch, no memset, no buffer of the engine, no saved plan, no
+ *     synchronisation: asynchronous on stream.  The block norms a numeric phase announced are forgotten (dst may be a data area).
+ *     0 on success and for nblk == 0; -1 for a null handle or array, negative counts, a rank outside 2 ... 4, a perm that is no permutation of
+ *     0 ... rank - 1, [src, src + src_len) overlapping [dst, dst + dst_len), and a list too long for one grid; -10 for complex_4 and unknown type codes. */
+int dbcsr_amd_tensor_permute_blocks(void* handle, libsmm_acc_data_t datatype, int64_t nblk, int rank, const int* perm, const int32_t* ext,
+  const int64_t* src_off, const int64_t* dst_off, const void* src, int64_t src_len, void* dst, int64_t dst_len, void* stream);
+
 /* Measurement helper (bench.py, roofline.fabric): what the L2 <-> Infinity-Cache fabric of the current device delivers, in TB/s -- a
  * plain streaming read of a 160 MB window by all CUs, and the block gather of the block-product dataflow (4232-byte blocks from
  * pseudo-random places of the window into LDS, whole 128-byte lines counted).  Takes well under a second; synchronises the device. */
