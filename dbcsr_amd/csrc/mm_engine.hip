@@ -40,6 +40,7 @@
 //                        mm_multivec.h, mm_rank_update.h, over the block walk of mm_block_walk.h), the block diagonal (mm_block_inverse.h), its product with a
 //                        matrix (mm_block_scale.h), the dense conversion (mm_dense.h) and the submatrix method (mm_submatrix.h)
 //   mm_engine_csr.h      the element CSR form (kernels: mm_csr.h)
+//   mm_engine_reblock.h  a matrix under another block structure (kernels: mm_reblock.h)
 //   mm_engine_tensor.h   block-sparse tensors: the permuting move (kernel: mm_tensor.h)
 // This file: create / destroy, the symbolic phase, and the numeric phase as a sequence -- product lists, choice, set-up, launch, plan bookkeeping.
 #include <hip/hip_runtime.h>
@@ -77,6 +78,7 @@
 #include "mm_dense.h"  // dense <-> block-sparse: to_dense, from_dense and the count half of create_from_dense
 #include "mm_submatrix.h"  // the submatrix method: batched dense principal submatrices out of the matrix and back onto its pattern
 #include "mm_csr.h"  // element CSR <-> block-sparse: to_csr (count, emit), from_csr and the blocks of a CSR
+#include "mm_reblock.h"  // a matrix under another block structure: the pieces of the source blocks and the gather
 #include "mm_tensor.h"  // block-sparse tensors: the permuting move of a list of blocks
 // The library comes in two builds (Makefile): the SHIPPING one holds what a multiply can run by itself -- the kernels listed above, their
 // symbolic phases, plan reuse -- and the LAB one (-DDBCSR_AMD_EXPERIMENTS, libdbcsr_acc_amd_lab.so) adds every dataflow and variant that
@@ -626,6 +628,7 @@ int dbcsr_amd_mm_numeric_z(void* handle, const double alpha[2], const dbcsr_amd_
 #include "mm_engine_elementwise.h"   // hadamard product, copy onto a pattern, functions of elements
 #include "mm_engine_blocklist.h"   // reserve, put and get blocks through a coordinate list
 #include "mm_engine_csr.h"   // the element CSR form: to_csr (count / apply), from_csr, the blocks of a CSR
+#include "mm_engine_reblock.h"   // re-blocking: the pieces of the source blocks, the gather
 #include "mm_engine_tensor.h"   // block-sparse tensors: the permuting move of a list of blocks
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 // mm_engine_blocklist.h -- part of mm_engine.hip (included inside extern "C", after mm_engine_elementwise.h, whose helpers it uses): the C-ABI entries on
-// a coordinate list of blocks -- dbcsr_amd_bcsr_reserve_count / _reserve_apply, dbcsr_amd_bcsr_put_blocks and dbcsr_amd_bcsr_get_blocks.  Kernels:
-// mm_blocklist.h.  Put, get and the first half of a reserve count work in Engine::bl_* and the scan's scratch alone: no work area of the symbolic phase
-// is touched and plan_invalidate is not called.  Only a reserve that creates blocks goes on into the work areas, as the union add does.
+// a coordinate list of blocks -- dbcsr_amd_bcsr_reserve_count / _reserve_apply / _reserve_apply_index, dbcsr_amd_bcsr_put_blocks and
+// dbcsr_amd_bcsr_get_blocks.  Kernels: mm_blocklist.h.  Put, get and the first half of a reserve count work in Engine::bl_* and the scan's scratch
+// alone: no work area of the symbolic phase is touched and plan_invalidate is not called.  Only a reserve that creates blocks goes on into the work
+// areas, as the union add does.
 #ifndef DBCSR_AMD_MM_ENGINE_BLOCKLIST_H
 #define DBCSR_AMD_MM_ENGINE_BLOCKLIST_H
 
@@ -103,6 +104,27 @@ int dbcsr_amd_bcsr_reserve_apply(void* handle, libsmm_acc_data_t datatype, const
                      E->prod_start.p);
   DBCSR_AMD_BY_TYPE(copy_onto_launch, st, m, dst);
   return check(hipGetLastError(), "dbcsr_amd_bcsr_reserve_apply", __FILE__, __LINE__);
+}
+
+// _reserve_apply without the data pass (the "Re-blocking" section of the header): col_i and blk_p of the counted union, nothing else -- for a caller
+// that writes every element of the new data area itself.  The same pending-state rules; no value is written, so announced block norms stay.
+int dbcsr_amd_bcsr_reserve_apply_index(void* handle, const dbcsr_amd_bcsr* m, dbcsr_amd_bcsr* dst, void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E || !m || !dst) return -1;
+  const bool pending = E->rsv_pending;
+  E->rsv_pending = false;
+  if (!pending || m->row_p != E->rsv_row_p || m->nblks != E->rsv_nblks_a || m->nblkrows != E->rsv_nblkrows || m->nblkcols != E->rsv_nblkcols ||
+      dst->nblkrows != m->nblkrows || dst->nblkcols != m->nblkcols || !dst->row_p || !dst->col_i || !dst->blk_p)
+    return -1;
+  plan_invalidate(E);  // this call uses the engine's work areas: the next multiply runs its own symbolic phase
+  hipStream_t st = stream_of(stream);
+  const int nbr = m->nblkrows, W = (m->nblkcols + 31) / 32;
+  if (E->prod_start.ensure(2 * (size_t)E->rsv_nblks + 2)) return -1;
+  dst->nblks = E->rsv_nblks;
+  hipLaunchKernelGGL(algebra_emit, grid_for((int64_t)nbr * W), dim3(256), 0, st, m->row_p, m->blk_p, E->cin_bm.p, E->cin_pre.p, m->row_p, m->blk_p,
+                     (const uint32_t*)nullptr, E->cin_pre.p, E->c_bm.p, E->c_pre.p, dst->row_p, E->c_blk_p_ws.p, nbr, W, dst->col_i, dst->blk_p,
+                     E->prod_start.p);
+  return check(hipGetLastError(), "dbcsr_amd_bcsr_reserve_apply_index", __FILE__, __LINE__);
 }
 
 int dbcsr_amd_bcsr_put_blocks(void* handle, libsmm_acc_data_t datatype, dbcsr_amd_bcsr* m, int64_t n, const int32_t* rows, const int32_t* cols,

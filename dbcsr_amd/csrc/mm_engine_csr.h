@@ -184,6 +184,6 @@ int dbcsr_amd_bcsr_csr_name_blocks(void* handle, int64_t n_rows, int64_t nnz, co
     hipLaunchKernelGGL(csr_name_blocks, grid_for(n_rows * 64), dim3(256), 0, st, crow, col, nnz, n_rows, roff, coff, nblkrows, nblkcols, rows, cols);
   return check(hipGetLastError(), "dbcsr_amd_bcsr_csr_name_blocks", __FILE__, __LINE__);
 }
-// (DBCSR_AMD_BY_TYPE stays defined for mm_engine_tensor.h, which follows this file and ends its life)
+// (DBCSR_AMD_BY_TYPE stays defined for mm_engine_reblock.h and mm_engine_tensor.h, which follow this file; the last one ends its life)
 
 #endif

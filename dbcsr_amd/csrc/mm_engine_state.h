@@ -205,6 +205,11 @@ struct Engine {
   CsrLen csr_len[kCsrLens];
   int csr_len_next = 0;
 
+  // ---- re-blocking (mm_engine_reblock.h): buffers that no other entry writes; nothing is pending in them between two calls ----
+  DevBuf<int64_t> rb_off;     // the running sums of the source's block sizes and of the new ones: roff, coff, new roff, new coff
+  DevBuf<int64_t> rb_pos;     // _reblock_name_blocks: the place of every source block's first piece [nblks + 1]
+  DevBuf<int> rb_i32;         // _reblock_name_blocks: per source block its pieces [nblks], then (first new block row, first new block column, column span)
+
   // ---- switches (mm_engine_env.h) ----
   Switches sw;      // the numeric phase's kernel families (mm_choose.h)
   LabSwitches lab;  // lab build only: no state in the shipping build

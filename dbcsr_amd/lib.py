@@ -60,6 +60,8 @@ MM_SYMBOLS = [
     "dbcsr_amd_bcsr_reserve_count", "dbcsr_amd_bcsr_reserve_apply", "dbcsr_amd_bcsr_put_blocks", "dbcsr_amd_bcsr_get_blocks",
     # element CSR (dbcsr_amd/csr.py)
     "dbcsr_amd_bcsr_to_csr_count", "dbcsr_amd_bcsr_to_csr_apply", "dbcsr_amd_bcsr_from_csr", "dbcsr_amd_bcsr_csr_name_blocks",
+    # re-blocking (dbcsr_amd/reblock.py)
+    "dbcsr_amd_bcsr_reblock_name_blocks", "dbcsr_amd_bcsr_reserve_apply_index", "dbcsr_amd_bcsr_reblock_gather",
     # block-sparse tensors (dbcsr_amd/tensor.py)
     "dbcsr_amd_tensor_permute_blocks",
 ]
@@ -248,6 +250,9 @@ def load_library(lab=False):
     L.dbcsr_amd_bcsr_to_csr_apply.argtypes = [vp, i32, BP, vp, vp, vp]
     L.dbcsr_amd_bcsr_from_csr.argtypes = [vp, i32, i64, i64, i64, vp, vp, vp, BP, vp]
     L.dbcsr_amd_bcsr_csr_name_blocks.argtypes = [vp, i64, i64, vp, vp, vp, vp, i32, i32, vp, vp, vp]
+    L.dbcsr_amd_bcsr_reblock_name_blocks.argtypes = [vp, BP, vp, vp, i32, i32, C.POINTER(i64), vp, vp, vp]
+    L.dbcsr_amd_bcsr_reserve_apply_index.argtypes = [vp, BP, BP, vp]
+    L.dbcsr_amd_bcsr_reblock_gather.argtypes = [vp, i32, BP, BP, vp]
     L.dbcsr_amd_tensor_permute_blocks.argtypes = [vp, i32, i64, i32, C.POINTER(i32), vp, vp, vp, vp, i64, vp, i64, vp]
     if lab:   # diagnostics of the experimental dataflows (dbcsr_amd/csrc/mm_lab_api.h): the shipping build does not export them
         L.dbcsr_amd_mm_tile_stats.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]

@@ -671,6 +671,40 @@ int dbcsr_amd_bcsr_from_csr(void* handle, libsmm_acc_data_t datatype, int64_t n_
 int dbcsr_amd_bcsr_csr_name_blocks(void* handle, int64_t n_rows, int64_t nnz, const int64_t* crow, const int32_t* col, const int32_t* row_blk_size,
   const int32_t* col_blk_size, int nblkrows, int nblkcols, int32_t* rows, int32_t* cols, void* stream);
 
+/* Re-blocking: a matrix under another block structure, without leaving the device and without leaving the block-sparse form (dbcsr_amd/reblock.py).
+ * The reference has the capability in dbcsr_complete_redistribute (a copy between matrices of different blockings: CP2K goes from atomic to molecular or
+ * clustered blocks with it) and, for tensors, in dbcsr_t_split_blocks; their sources could not be consulted: the two rules below are the semantics of
+ * this library.  A is a matrix without symmetry (a stored triangle is served as the blocks it stores: dbcsr_amd_bcsr_desymmetrized expands it first),
+ * (rs', cs') a second block structure whose sizes are >= 1 and have the same sums.
+ *   pattern  a new block (I, J) is stored iff its element rectangle intersects the rectangle of at least one block that A's index names.  Values play no
+ *            part: a stored block full of zeros counts, the holes of an unpacked data area are never read.
+ *   values   an element of a stored new block is the element of A at the same (row, column), bit for bit (-0.0, NaN and +-Inf included), where A's index
+ *            names a block there, and +0.0 elsewhere.
+ * Blocks are column-major as everywhere.  Same types as the algebra above.  The three entries work in buffers of their own (and the scan's scratch): no
+ * saved plan and no work area of the symbolic phase is touched by _reblock_name_blocks and _reblock_gather.
+ *   _reblock_name_blocks  the counterpart of _csr_name_blocks.  A source block covers a span of new block rows and a span of new block columns, found by
+ *     binary searches in the running sums of the new sizes (new_row_blk_size [new_nblkrows], new_col_blk_size [new_nblkcols], device); it names
+ *     rowspan x colspan pieces.  Two calls.  With rows == cols == NULL: *n_pieces (host) <- the total; synchronises once.  With both lists (int32
+ *     [*n_pieces], device; *n_pieces is then read as their length): rows[t], cols[t] <- the new block of piece t, the pieces of one source block
+ *     together; nothing is stored at or behind *n_pieces; asynchronous on stream.  The list names a new block once per source block that meets it; it
+ *     is what _reserve_count takes on an empty matrix of the new structure.  A source block outside the new structure or of no element names nothing.
+ *     -1 for null arguments, one list without the other, and a total of 2^31 - 1 pieces or more.
+ *   _reserve_apply_index  _reserve_apply without the data pass: of what the pending _reserve_count counted it writes dst->col_i and dst->blk_p only (and
+ *     sets dst->nblks), as _filter_apply_index stands beside _filter_apply -- so that a caller who writes every element of the new data area itself
+ *     need not have it zero-filled first.  dst->data is not read.  The same pending-state rules: an apply without a pending count, a second one, one
+ *     after anything else took the work areas, or one for another matrix than the counted one is refused (-1) and writes nothing.
+ *   _reblock_gather  the move.  For every block the index of dst names, every element is written exactly once by the values rule with src as A, and
+ *     nothing else: no index array, no hole of an unpacked dst.  dst may be any pattern of any structure with the same sums: the new matrix that the
+ *     two entries above made, or an existing one (the keep_sparsity form and the way back).  One workgroup per (new block, tile of at most 32 x 32
+ *     elements); a lookup table in LDS holds the data offset of every source block that crosses the tile; 16-byte stores aligned on dst; no atomics, no
+ *     scratch, no memset; every offset is formed in 64 bits; the same bits on every call.  It synchronises nothing, except when it meets a set of block
+ *     sizes for the first time, for their sums, as _to_dense remembers them.  The block norms a numeric phase announced are forgotten.
+ *     -1 for null arguments, sums that differ and src->data == dst->data; -10 for other type codes; 0 with nothing done for a dst without blocks. */
+int dbcsr_amd_bcsr_reblock_name_blocks(void* handle, const dbcsr_amd_bcsr* src, const int32_t* new_row_blk_size, const int32_t* new_col_blk_size,
+  int new_nblkrows, int new_nblkcols, int64_t* n_pieces, int32_t* rows, int32_t* cols, void* stream);
+int dbcsr_amd_bcsr_reserve_apply_index(void* handle, const dbcsr_amd_bcsr* m, dbcsr_amd_bcsr* dst, void* stream);
+int dbcsr_amd_bcsr_reblock_gather(void* handle, libsmm_acc_data_t datatype, const dbcsr_amd_bcsr* src, dbcsr_amd_bcsr* dst, void* stream);
+
 /* Tensors: the one device primitive under the block-sparse tensor interface (dbcsr_amd/tensor.py, the dbcsr_t_* of the reference's src/tensors).  A tensor
  * is stored as a matrix without symmetry: a mapping (map1 | map2) folds its dimensions into block rows and block columns, the first entry of each tuple
  * running fastest, for the block index and inside a block alike; a stored block is the Fortran array of the tensor block with its dimensions in the order
