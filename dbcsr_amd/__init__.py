@@ -9,7 +9,7 @@ from .lib import load_library, library_path  # noqa: F401
 from .operations import dbcsr_add, dbcsr_add_on_diag, dbcsr_dot, dbcsr_frobenius_norm, dbcsr_scale, dbcsr_trace  # noqa: F401
 from .operations import (dbcsr_get_diag, dbcsr_gershgorin_norm, dbcsr_maxabs_norm, dbcsr_norm, dbcsr_norm_column,  # noqa: F401
                          dbcsr_norm_frobenius, dbcsr_norm_gershgorin, dbcsr_norm_maxabsnorm, dbcsr_scale_by_vector, dbcsr_set_diag)
-from .operations import dbcsr_matvec, dbcsr_multivec, dbcsr_rank_update  # noqa: F401
+from .operations import dbcsr_matvec, dbcsr_multiply_dense, dbcsr_multivec, dbcsr_rank_update  # noqa: F401
 from .operations import dbcsr_get_block_diag, dbcsr_invert_block_diag, dbcsr_scale_by_block_diag  # noqa: F401
 from .operations import dbcsr_create_from_dense, dbcsr_from_dense, dbcsr_to_dense  # noqa: F401
 from .operations import dbcsr_copy, dbcsr_function_of_elements, dbcsr_hadamard_product  # noqa: F401
@@ -27,6 +27,7 @@ __all__ = ["load_library", "library_path", "dbcsr_reblock", "dbcsr_reblock_into"
            "dbcsr_add", "dbcsr_scale", "dbcsr_add_on_diag", "dbcsr_trace", "dbcsr_dot", "dbcsr_frobenius_norm",
            "dbcsr_maxabs_norm", "dbcsr_gershgorin_norm", "dbcsr_norm", "dbcsr_norm_frobenius", "dbcsr_norm_maxabsnorm", "dbcsr_norm_gershgorin",
            "dbcsr_norm_column", "dbcsr_get_diag", "dbcsr_set_diag", "dbcsr_scale_by_vector", "dbcsr_matvec", "dbcsr_multivec", "dbcsr_rank_update",
+           "dbcsr_multiply_dense",
            "dbcsr_get_block_diag", "dbcsr_invert_block_diag", "dbcsr_scale_by_block_diag", "dbcsr_to_dense", "dbcsr_from_dense", "dbcsr_create_from_dense",
            "dbcsr_hadamard_product", "dbcsr_copy", "dbcsr_function_of_elements", "dbcsr_func_inverse", "dbcsr_func_tanh", "dbcsr_func_dtanh",
            "dbcsr_func_ddtanh", "dbcsr_func_artanh", "dbcsr_func_sin", "dbcsr_func_dsin", "dbcsr_func_ddsin", "dbcsr_func_asin", "dbcsr_func_cos",

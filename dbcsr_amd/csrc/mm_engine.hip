@@ -36,8 +36,8 @@
 //   mm_engine_plan.h     plan reuse
 //   mm_engine_lab.h      lab build: hosts of the experimental dataflows and their family switch
 //   mm_engine_ops.h      init_c, crop, filter, checksum, fill, transpose, twin moves, statistics
-//   mm_engine_algebra.h  add (count / apply), add_on_diag pieces, trace, dot, norm, norms and vectors, matvec, multivec, rank update (kernels: mm_algebra.h,
-//                        mm_multivec.h, mm_rank_update.h, over the block walk of mm_block_walk.h), the block diagonal (mm_block_inverse.h), its product with a
+//   mm_engine_algebra.h  add (count / apply), add_on_diag pieces, trace, dot, norm, norms and vectors, matvec, multivec, rank update, multiply_dense (kernels:
+//                        mm_algebra.h, mm_multivec.h, mm_rank_update.h, mm_spmm.h, over the block walk of mm_block_walk.h), the block diagonal (mm_block_inverse.h), its product with a
 //                        matrix (mm_block_scale.h), the dense conversion (mm_dense.h) and the submatrix method (mm_submatrix.h)
 //   mm_engine_csr.h      the element CSR form (kernels: mm_csr.h)
 //   mm_engine_reblock.h  a matrix under another block structure (kernels: mm_reblock.h)
@@ -73,6 +73,7 @@
 #include "mm_blocklist.h"  // a coordinate list of blocks: reserve, put and get
 #include "mm_multivec.h"  // the matrix times several dense vectors
 #include "mm_rank_update.h"  // the rank-k update on the stored pattern
+#include "mm_spmm.h"  // the matrix times a dense matrix on the MFMA
 #include "mm_block_inverse.h"  // the block diagonal: its copy and the batched inverse of its blocks
 #include "mm_block_scale.h"  // a block diagonal applied to a matrix in place
 #include "mm_dense.h"  // dense <-> block-sparse: to_dense, from_dense and the count half of create_from_dense

@@ -1,9 +1,9 @@
 // mm_engine_algebra.h -- part of mm_engine.hip (included inside extern "C", after mm_engine_ops.h): the C-ABI operations between multiplies --
 // dbcsr_amd_bcsr_add_count / _add_apply, the pieces of dbcsr_add_on_diag (dbcsr_amd_bcsr_diag_count / _diag_fill / _diag_shift), dbcsr_amd_bcsr_trace,
-// _dot, _norm2, and the norms and vectors: dbcsr_amd_bcsr_maxabs, _row_sums, _col_sums, _gershgorin, _get_diag, _set_diag, _scale_by_vector, _matvec, _multivec, _rank_update,
+// _dot, _norm2, and the norms and vectors: dbcsr_amd_bcsr_maxabs, _row_sums, _col_sums, _gershgorin, _get_diag, _set_diag, _scale_by_vector, _matvec, _multivec, _rank_update, _multiply_dense,
 // the block diagonal: dbcsr_amd_bcsr_block_diag_count / _apply / _invert / _multiply, and the dense conversion: dbcsr_amd_bcsr_to_dense / _from_dense_apply /
 // _from_dense_count, and the submatrix method: dbcsr_amd_bcsr_submatrix_gather / _submatrix_scatter.
-// Kernels: mm_algebra.h, mm_multivec.h, mm_rank_update.h, mm_block_inverse.h, mm_block_scale.h, mm_dense.h, mm_submatrix.h. The reductions, the diagonal pieces, the same-pattern add and the norms and vectors use buffers of their own (Engine::alg_*) and the
+// Kernels: mm_algebra.h, mm_multivec.h, mm_rank_update.h, mm_spmm.h, mm_block_inverse.h, mm_block_scale.h, mm_dense.h, mm_submatrix.h. The reductions, the diagonal pieces, the same-pattern add and the norms and vectors use buffers of their own (Engine::alg_*) and the
 // scan's scratch, which no saved plan depends on (the checksum uses it the same way): they do NOT invalidate the plan.  The union add borrows the
 // symbolic phase's bitmaps and prefix arrays and invalidates it, as filter and crop do.
 #ifndef DBCSR_AMD_MM_ENGINE_ALGEBRA_H
@@ -733,6 +733,70 @@ int dbcsr_amd_bcsr_rank_update(void* handle, libsmm_acc_data_t datatype, char tr
   if (vector_offsets(E, st, a, &roff, &coff)) return -1;
   DBCSR_AMD_BY_TYPE(rank_update_launch, st, a, roff, coff, datatype == dbcsr_type_complex_8 && trans == 'C' ? 1 : 0, alpha, beta, mode, nrhs, x, n_x, ldx, y, n_y, ldy);
   return check(hipGetLastError(), "dbcsr_amd_bcsr_rank_update", __FILE__, __LINE__);
+}
+
+// ---- matrix times a dense matrix on the MFMA (kernels: mm_spmm.h) ----------------------------------------------------------------------------------------
+extern "C++" {
+static inline int spmm_pass_bits(const MatvecPass& p) {
+  return (p.on ? kSpmmRowsOn : 0) | (p.skip_diag ? kSpmmSkipDiag : 0) | (p.conj ? kSpmmConj : 0) | (p.sign < 0.0 ? kSpmmNegate : 0);
+}
+
+// (the caller built the offsets, and the column list when the column pass is on)
+template <typename T>
+static void spmm_launch(Engine* E, hipStream_t st, const dbcsr_amd_bcsr* a, const MatvecPass& rp, const MatvecPass& cp, const int64_t* roff,
+                        const int64_t* coff, const int64_t* total, const double alpha[2], const double beta[2], int mode, int ncol, const void* x,
+                        int64_t n_x, int64_t ldx, void* y, int64_t n_y, int64_t ldy, int layout) {
+  using Acc = typename MatvecAcc<T>::type;
+  const int beta_zero = (mode & kMatvecBetaZero) ? 1 : 0;
+  if (mode & kMatvecNoProduct) {
+    hipLaunchKernelGGL((spmm_scale<T>), grid_for(n_y * ncol), dim3(256), 0, st, static_cast<T*>(y), n_y, ncol, ldy, layout, total, algebra_scalar<T>(beta),
+                       beta_zero);
+    return;
+  }
+  const int nb = rp.on ? a->nblkrows : a->nblkcols, G = (ncol + kSpmmCols - 1) / kSpmmCols;
+  const int* col_p = cp.on ? E->alg_col_p.p : nullptr;
+  const int* list = cp.on ? E->alg_list.p : nullptr;
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((int64_t)nb * G)), dim3(256), 0, st, a->row_p, a->col_i, col_p, list, a->blk_p, static_cast<const T*>(a->data),
+                       a->row_blk_size, a->col_blk_size, roff, coff, nb, G, spmm_pass_bits(rp), spmm_pass_bits(cp), aligned16(a->data),
+                       static_cast<const T*>(x), n_x, ldx, static_cast<T*>(y), n_y, ldy, ncol, algebra_scalar<Acc>(alpha), algebra_scalar<Acc>(beta),
+                       beta_zero);
+  };
+  if (layout == 0) launch(spmm_product<T, 0>);
+  else launch(spmm_product<T, 1>);
+}
+}  // extern "C++"
+
+int dbcsr_amd_bcsr_multiply_dense(void* handle, libsmm_acc_data_t datatype, char trans, const double alpha[2], const dbcsr_amd_bcsr* a, int kind, int ncol,
+                                  const void* x, int64_t n_x, int64_t ldx, const double beta[2], void* y, int64_t n_y, int64_t ldy, int layout,
+                                  void* stream) {
+  Engine* E = static_cast<Engine*>(handle);
+  if (!E || !alpha || !a || !beta || n_x < 0 || n_y < 0 || ncol < 0 || (layout != 0 && layout != 1)) return -1;
+  if (layout == 0 ? (ldx < ncol || ldy < ncol) : (ldx < n_x || ldy < n_y)) return -1;
+  if (ncol > 0 && ((n_x > 0 && !x) || (n_y > 0 && !y))) return -1;
+  if (!matvec_args_ok(trans, kind, a)) return -1;
+  if (!algebra_type(datatype)) return -10;
+  const size_t esize = algebra_esize(datatype);
+  if (ncol > 0 && n_x > 0 && n_y > 0) {   // the element ranges of X and Y must not overlap
+    const size_t ex = layout == 0 ? (size_t)(n_x - 1) * (size_t)ldx + (size_t)ncol : (size_t)(ncol - 1) * (size_t)ldx + (size_t)n_x;
+    const size_t ey = layout == 0 ? (size_t)(n_y - 1) * (size_t)ldy + (size_t)ncol : (size_t)(ncol - 1) * (size_t)ldy + (size_t)n_y;
+    const uintptr_t x0 = reinterpret_cast<uintptr_t>(x), y0 = reinterpret_cast<uintptr_t>(y);
+    if (x0 < y0 + esize * ey && y0 < x0 + esize * ex) return -1;
+  }
+  hipStream_t st = stream_of(stream);
+  if (ncol == 0 || n_y == 0 || a->nblkrows == 0 || a->nblkcols == 0) return 0;   // (no element of Y below the full length: nothing to write)
+  bool product = false;   // alpha == 0: A and X are not read; an empty matrix: Y <- beta Y
+  const int mode = product_mode(datatype, alpha, beta, a->nblks > 0, &product);
+  MatvecPass rp = {0, 0, 0, 1.0}, cp = rp;
+  if (product) matvec_passes(kind, trans, &rp, &cp);
+  const int64_t G = ((int64_t)ncol + kSpmmCols - 1) / kSpmmCols;
+  if ((int64_t)std::max(a->nblkrows, a->nblkcols) * G > INT32_MAX || n_y > (int64_t)INT32_MAX * 256 / ncol) return -1;   // (the grids)
+  const int64_t *roff = nullptr, *coff = nullptr;
+  if (vector_offsets(E, st, a, &roff, &coff)) return -1;
+  if (cp.on && col_list_build(E, st, a)) return -1;
+  const int64_t* total = trans == 'N' ? roff + a->nblkrows : coff + a->nblkcols;   // the full rows of op(A)
+  DBCSR_AMD_BY_TYPE(spmm_launch, E, st, a, rp, cp, roff, coff, total, alpha, beta, mode, ncol, x, n_x, ldx, y, n_y, ldy, layout);
+  return check(hipGetLastError(), "dbcsr_amd_bcsr_multiply_dense", __FILE__, __LINE__);
 }
 // ---- block diagonal (kernels: mm_block_inverse.h) ---------------------------------------------------------------------------------------------------------
 extern "C++" {

@@ -45,7 +45,7 @@ MM_SYMBOLS = [
     # norms and vectors
     "dbcsr_amd_bcsr_maxabs", "dbcsr_amd_bcsr_row_sums", "dbcsr_amd_bcsr_col_sums", "dbcsr_amd_bcsr_gershgorin", "dbcsr_amd_bcsr_get_diag",
     "dbcsr_amd_bcsr_set_diag", "dbcsr_amd_bcsr_scale_by_vector", "dbcsr_amd_bcsr_matvec", "dbcsr_amd_bcsr_multivec",
-    "dbcsr_amd_bcsr_rank_update",
+    "dbcsr_amd_bcsr_rank_update", "dbcsr_amd_bcsr_multiply_dense",
     # block diagonal
     "dbcsr_amd_bcsr_block_diag_count", "dbcsr_amd_bcsr_block_diag_apply", "dbcsr_amd_bcsr_block_diag_invert",
     # block diagonal times matrix
@@ -229,6 +229,7 @@ def load_library(lab=False):
     L.dbcsr_amd_bcsr_matvec.argtypes = [vp, i32, C.c_char, Z, BP, i32, vp, i64, Z, vp, i64, vp]
     L.dbcsr_amd_bcsr_multivec.argtypes = [vp, i32, C.c_char, Z, BP, i32, i32, vp, i64, i64, Z, vp, i64, i64, vp]
     L.dbcsr_amd_bcsr_rank_update.argtypes = [vp, i32, C.c_char, Z, i32, vp, i64, i64, vp, i64, i64, Z, BP, vp]
+    L.dbcsr_amd_bcsr_multiply_dense.argtypes = [vp, i32, C.c_char, Z, BP, i32, i32, vp, i64, i64, Z, vp, i64, i64, i32, vp]
     L.dbcsr_amd_bcsr_block_diag_count.argtypes = [vp, BP, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32), vp]
     L.dbcsr_amd_bcsr_block_diag_apply.argtypes = [vp, i32, BP, BP, vp]
     L.dbcsr_amd_bcsr_block_diag_invert.argtypes = [vp, i32, BP, i32, C.POINTER(i64), vp]

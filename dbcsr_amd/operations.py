@@ -15,6 +15,8 @@
     dbcsr_matvec(matrix, vec_in, vec_out, alpha, beta, trans)   y <- alpha*op(A)*x + beta*y with dense device vectors (not a mirror, see there)
     dbcsr_multivec(matrix, vecs_in, vecs_out, alpha, beta, trans)  Y <- alpha*op(A)*X + beta*Y with nrhs dense device vectors at once: A is read once
     dbcsr_rank_update(matrix, vecs_x, vecs_y, alpha, beta, trans)  A_IJ <- beta*A_IJ + alpha*X_I*op(Y_J) on the stored blocks only (not a mirror, see there)
+    dbcsr_multiply_dense(matrix, dense_in, dense_out, alpha, beta, trans)  Y <- alpha*op(A)*X + beta*Y with a dense operand of many columns, row by row
+                                                                or column by column, on the matrix cores (not a mirror, see there)
     dbcsr_get_block_diag(matrix)                                a new matrix of the diagonal blocks the matrix stores
     dbcsr_invert_block_diag(matrix, check)                      every stored diagonal block <- its inverse, in place (not a mirror, see there)
     dbcsr_scale_by_block_diag(matrix, diag, side, trans, alpha) A_IJ <- alpha*op(D_I)*A_IJ ("left"), alpha*A_IJ*op(D_J) ("right") or both, in place (not a mirror)
@@ -438,7 +440,9 @@ def dbcsr_multivec(matrix, vecs_in, vecs_out=None, alpha=1.0, beta=0.0, trans="N
     data type with stride(1) == 1 and stride(0) >= nrhs -- a contiguous tensor, or a column slice of a wider one.  trans, the symmetries, alpha == 0
     and beta == 0 are dbcsr_matvec's, per column; so are the checks.  The padding columns of a slice are never written.  vecs_out=None (then beta
     must be 0) allocates (n_y, nrhs) on the matrix' device and stream.  One column is served by the same kernels, not by dbcsr_matvec.  The two
-    tensors must not overlap.  Asynchronous on the stream; returns vecs_out."""
+    tensors must not overlap.  For a dense operand of hundreds of columns, or one stored column by column, see dbcsr_multiply_dense (matrix cores, no
+    partial sums): on the benchmark's 23 x 23 operand this function is the faster one at 16 and 32 columns (0.57 and 0.79 of its time) and the
+    slower one from 48 columns on (1.06 of its time at 48, 1.22 at 64, 1.57 at 1024; profiles/multiply_dense.txt).  Asynchronous on the stream; returns vecs_out."""
     sym = _check_symmetry("dbcsr_multivec", matrix)
     if trans not in ("N", "T", "C"):
         raise ValueError("dbcsr_multivec: trans must be 'N', 'T' or 'C', got %r" % (trans,))
@@ -535,6 +539,116 @@ def dbcsr_rank_update(matrix, vecs_x, vecs_y=None, alpha=1.0, beta=1.0, trans="T
                                         vecs_y.data_ptr() if n_cols and nrhs else None, n_cols, ldy, _z(beta), C.byref(d), st.ptr)
     if rc != 0:
         raise RuntimeError("dbcsr_amd_bcsr_rank_update failed (%d)" % rc)
+
+
+# ---- matrix times a dense matrix ---------------------------------------------------------------------------------------------------------------------
+def _dense_layouts(shape, strides):
+    """(ld row by row or None, ld column by column or None) of a 2-D tensor of this shape and these strides: row by row is stride(1) == 1 and
+    stride(0) = ld >= ncol, column by column stride(0) == 1 and stride(1) = ld >= n.  The stride of a dimension of one element, or of none, says nothing:
+    a tensor with one row or one column fits both.  Plain integers in and out: no device is needed."""
+    n, ncol = shape
+    s0, s1 = strides
+    by_row = by_col = None
+    if (ncol <= 1 or s1 == 1) and (n <= 1 or s0 >= max(ncol, 1)):
+        by_row = s0 if n > 1 else max(ncol, 1)
+    if (n <= 1 or s0 == 1) and (ncol <= 1 or s1 >= max(n, 1)):
+        by_col = s1 if ncol > 1 else max(n, 1)
+    return by_row, by_col
+
+
+def _check_dense_operand(name, matrix, what, t, n):
+    """a 2-D device tensor of n rows of the matrix' data type in one of the two layouts: checked before any call of the library"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s: %s must be a torch tensor" % (name, what))
+    if t.dtype != matrix.dtype:
+        raise TypeError("%s: %s has data type %r, expected %r" % (name, what, t.dtype, matrix.dtype))
+    if t.device != matrix.row_p.device:
+        raise ValueError("%s: %s is not on the matrix' device" % (name, what))
+    if t.dim() != 2 or t.shape[0] != n:
+        raise ValueError("%s: %s must be a 2-D tensor with %d rows" % (name, what, n))
+    layouts = _dense_layouts(tuple(t.shape), t.stride())
+    if layouts == (None, None):
+        raise ValueError("%s: %s must be row by row (stride(1) == 1, stride(0) >= ncol) or column by column (stride(0) == 1, stride(1) >= n), got "
+                         "strides %r" % (name, what, tuple(t.stride())))
+    return layouts
+
+
+def dbcsr_multiply_dense(matrix, dense_in, dense_out=None, alpha=1.0, beta=0.0, trans="N", engine=None, stream=None):
+    """dense_out <- alpha * op(A) * dense_in + beta * dense_out with a dense operand of many columns, on the matrix cores: the sparse matrix times the
+    coefficient matrix of every SCF step (H C and S C in OT and in the diagonalisation).  NOT a mirror of a routine of the reference: it serves the
+    call CP2K makes as cp_dbcsr_sm_fm_multiply, with dense device tensors in place of full matrices, and does not claim that name.  It is the forward
+    direction of dbcsr_rank_update and runs on the same v_mfma_f64_16x16x4_f64 core.
+    dense_in is (n_x, ncol), dense_out (n_y, ncol): 2-D device tensors of the matrix' data type, BOTH in the same layout -- row by row (stride(1) == 1,
+    stride(0) = ld >= ncol: dbcsr_multivec's layout, a contiguous tensor or a column slice of a wider basis) or column by column (stride(0) == 1,
+    stride(1) = ld >= n: a Fortran full matrix, t.T of a contiguous (ncol, n) tensor, or a window of leading dimension ld).  A tensor with one row or
+    one column fits both and takes the layout of the other tensor (row by row when both do).  Mixed layouts: ValueError.
+    trans is 'N', 'T' or 'C' (conjugate transpose; real data: 'T'); n_x is the full column count of op(A), n_y its full row count.  With symmetry
+    'S' / 'A' (real data) or 'H' / 'K' (complex data) the matrix is a stored triangle with a square structure and the product is that of the
+    desymmetrized matrix.  beta == 0: dense_out is not read (a NaN in it does not reach the result); alpha == 0: the matrix and dense_in are not read and
+    dense_out <- beta * dense_out in the data's own precision.  dense_out=None (then beta must be 0) allocates the result in dense_in's layout on the
+    matrix' device and stream.  The two tensors must not overlap (ValueError).  float64, float32 and complex128: products and sums in double / complex
+    double, alpha and beta applied in double, one rounding per element.  Every element of the (n_y, ncol) window is written exactly once -- the rows
+    of a block row that stores nothing become beta * dense_out, +0.0 for beta == 0 -- and nothing outside it: padding columns or rows of a window keep
+    their bits.  One workgroup owns its piece of the result from the first block to the end: no atomics, no partial sums, the same bits on every call;
+    within one layout the bits of a column depend neither on its position nor on how many columns come with it.  Rows and columns outside a block are
+    never loaded: an Inf or NaN in row r of dense_in reaches only the rows of the result whose row of op(A) stores an element in column r.  No index
+    array is written and no saved plan is touched.  Which width is whose (profiles/multiply_dense.txt, the benchmark's 23 x 23 operand, float64): at 16
+    and 32 columns dbcsr_multivec is faster (this function takes 1.75 and 1.27 of its time), from 48 columns on this function is (0.94 of its time
+    at 48, 0.82 at 64, 0.69 at 256, 0.64 at 1024; column by column from 64 on: 0.95 / 0.76 / 0.74 of dbcsr_multivec with the two transposing copies).
+    It LOSES to dbcsr_create_from_dense -> dbcsr_multiply -> dbcsr_to_dense at every width measured (1.02 to 1.79 of that route's time) where the
+    dense operand fits as a block-sparse matrix.  Every check comes before any call of the library.  Asynchronous on the stream; returns dense_out."""
+    name = "dbcsr_multiply_dense"
+    sym = _check_symmetry(name, matrix)
+    if trans not in ("N", "T", "C"):
+        raise ValueError("%s: trans must be 'N', 'T' or 'C', got %r" % (name, trans))
+    matrix.dtype_code
+    kind = -1
+    if sym != "N":
+        kind = matrix.symmetry_kind()
+        _check_square(name, matrix)
+    _check_scalar(name, matrix, alpha, beta)
+    n_rows, n_cols = _full_size(matrix.row_blk_size), _full_size(matrix.col_blk_size)
+    n_x, n_y = (n_cols, n_rows) if trans == "N" else (n_rows, n_cols)
+    x_row, x_col = _check_dense_operand(name, matrix, "dense_in", dense_in, n_x)
+    ncol = dense_in.shape[1]
+    if dense_out is None:
+        if beta != 0:
+            raise ValueError("%s: beta != 0 needs a dense_out" % name)
+        layout = 0 if x_row is not None else 1
+        ldx = x_row if layout == 0 else x_col
+        ldy = max(ncol, 1) if layout == 0 else max(n_y, 1)
+    else:
+        y_row, y_col = _check_dense_operand(name, matrix, "dense_out", dense_out, n_y)
+        if dense_out.shape[1] != ncol:
+            raise ValueError("%s: dense_in has %d columns, dense_out %d" % (name, ncol, dense_out.shape[1]))
+        if x_row is not None and y_row is not None:
+            layout, ldx, ldy = 0, x_row, y_row
+        elif x_col is not None and y_col is not None:
+            layout, ldx, ldy = 1, x_col, y_col
+        else:
+            raise ValueError("%s: dense_in and dense_out must be in the same layout (strides %r and %r)" %
+                             (name, tuple(dense_in.stride()), tuple(dense_out.stride())))
+        size = dense_in.element_size()
+        ex = (n_x - 1) * ldx + ncol if layout == 0 else (ncol - 1) * ldx + n_x
+        ey = (n_y - 1) * ldy + ncol if layout == 0 else (ncol - 1) * ldy + n_y
+        x0, y0 = dense_in.data_ptr(), dense_out.data_ptr()
+        if ncol and n_x and n_y and x0 < y0 + size * ey and y0 < x0 + size * ex:
+            raise ValueError("%s: dense_in and dense_out overlap" % name)
+    E = engine or default_engine()
+    st = StreamHandle(stream)
+    if dense_out is None:
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            if layout == 0:
+                dense_out = torch.empty((n_y, ncol), dtype=matrix.dtype, device=matrix.row_p.device)
+            else:
+                dense_out = torch.empty((ncol, n_y), dtype=matrix.dtype, device=matrix.row_p.device).t()
+    d = matrix.desc()
+    rc = E.L.dbcsr_amd_bcsr_multiply_dense(E.h, matrix.dtype_code, trans.encode(), _z(alpha), C.byref(d), kind, ncol,
+                                           dense_in.data_ptr() if n_x and ncol else None, n_x, ldx, _z(beta),
+                                           dense_out.data_ptr() if n_y and ncol else None, n_y, ldy, layout, st.ptr)
+    if rc != 0:
+        raise RuntimeError("dbcsr_amd_bcsr_multiply_dense failed (%d)" % rc)
+    return dense_out
 
 
 # ---- block diagonal --------------------------------------------------------------------------------------------------------------------------------

@@ -442,6 +442,24 @@ int dbcsr_amd_bcsr_multivec(void* handle, libsmm_acc_data_t datatype, char trans
  *               write stays inside the blocks that the index names. */
 int dbcsr_amd_bcsr_rank_update(void* handle, libsmm_acc_data_t datatype, char trans, const double alpha[2], int nrhs, const void* x, int64_t n_x,
   int64_t ldx, const void* y, int64_t n_y, int64_t ldy, const double beta[2], dbcsr_amd_bcsr* a, void* stream);
+/*   _multiply_dense  Y <- alpha op(A) X + beta Y with a dense operand of many columns, on the matrix cores: the forward direction of _rank_update, what
+ *               cp_dbcsr_sm_fm_multiply does (H C, S C).  X is n_x x ncol, Y is n_y x ncol, dense DEVICE matrices of the matrix' data type in the SAME
+ *               layout: layout 0 row by row (element (i, v) at i ld + v, ld >= ncol: _multivec's), layout 1 column by column (element (i, v) at
+ *               i + v ld, ld >= n_x / n_y: a Fortran full matrix or a window of one).  trans, kind, alpha == 0, beta == 0 and the empty matrix are
+ *               _multivec's.  One workgroup owns a block row of op(A) and 64 columns of Y from the first block to the epilogue: no partial matrices,
+ *               no floating-point atomics, the same bits on every call; within one layout the bits of a column depend neither on its position nor
+ *               on the other columns.  Products and sums in double / complex double (fp32 data converted first), alpha and beta applied in double,
+ *               one rounding per element.  Every element of Y in rows below n_y and below the full row count of op(A) and in columns below ncol is
+ *               written exactly once -- a block row that stores nothing gets beta y (in double, one rounding), +0 for beta == 0 -- and nothing
+ *               else is written.  Every read of X stays in rows below n_x and columns below ncol; rows and columns outside a block are never
+ *               loaded, they enter as true zeros: an Inf or NaN in row r of X reaches only the rows of Y whose row of op(A) stores an element in
+ *               column r.  Buffers of its own (the offsets and the per-column lists of the algebra; no sums), a saved plan stays; asynchronous, no
+ *               synchronisation.  -1 for a null argument, a bad trans, kind or layout, kind >= 0 with nblkrows != nblkcols, ncol < 0, n_x < 0 or
+ *               n_y < 0, ld below ncol (layout 0) or below n_x / n_y (layout 1), when the element ranges of X and Y intersect, and for grids above
+ *               INT32_MAX; -10 for a data type the algebra does not know; 0 with nothing written for ncol == 0 or n_y == 0. */
+int dbcsr_amd_bcsr_multiply_dense(void* handle, libsmm_acc_data_t datatype, char trans, const double alpha[2], const dbcsr_amd_bcsr* a,
+  int kind /* -1; 0 ... 3: S A H K */, int ncol, const void* x, int64_t n_x, int64_t ldx, const double beta[2], void* y, int64_t n_y, int64_t ldy,
+  int layout /* 0: row by row; 1: column by column */, void* stream);
 
 /* Block diagonal: dbcsr_get_block_diag of the reference, and the batched inversion of the diagonal blocks that CP2K does on the host with an iterator and
  * invmat -- the initial guess X0 = blockdiag(S)^-1 of a Hotelling / Newton-Schulz inverse, and the block-Jacobi preconditioner blockdiag(A)^-1 that
